@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the MF + BPR training hot path on MI355X (contract in the task brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, ONE timed region of K steps, the
+outputs (--dump-outputs DIR: the tables the timed steps left, see `dump_outputs`) and the line.  Everything else the
+benchmark measures or checks - three timed regions instead of one, the `secondary` leg, the CPU baseline, the `extra`
+legs, the device copy rate, and at N>1 the replica check, the sweeps and the one-GPU reference - runs with --full only.
 
 `python bench.py --gpus N` with N > 1 and no launcher around it spawns its N ranks itself (one process
 per GPU, RCCL) and refuses to run when the box has fewer than N GPUs: it never reports a smaller job
@@ -16,7 +21,7 @@ starts; the per-epoch plan builds (the device side of DataLoader(shuffle=True)) 
 timed steps ARE timed.  Default timed region: two epochs of full batches.
 
 N=1  : BASELINE.json configs[1]  U=1M, I=100k, nnz=50M, d=64 (uniform ids), SGD, lr .01, reg .001 - the line's
-       `value`.  The same run then measures, as `secondary`, the pure-HBM regime: the table shapes of configs[2]
+       `value`.  With --full the same run then measures, as `secondary`, the pure-HBM regime: the table shapes of configs[2]
        (10M users x 1M items: P 2.56 GB, Q 256 MB, both beyond the 256 MB Infinity Cache) on this one GPU at the same
        2M-interaction steps, with the interaction count cut to 100M (a shorter epoch; what a step moves depends on the
        tables and the batch, not on the number of batches per epoch), and the CPU baseline.
@@ -26,7 +31,8 @@ N>1  : BASELINE.json configs[2]  U=10M, I=1M, nnz=500M split by user over the N 
        version, the ranks' devices, a replica check (a small fit through `MF.fit` sharded over the ranks against the
        same fit on one GPU: epoch losses and Q), the per-step split into compute and exposed exchange, a sweep over
        B_local x exchange slices with the >= 6x verdict per point, and - unless --no-ref - the SAME workload on one GPU
-       measured by rank 0 afterwards.  `--workload c2` weak-scales configs[1] instead.
+       measured by rank 0 afterwards (the replica check, the sweeps and the reference with --full only).
+       `--workload c2` weak-scales configs[1] instead.
 
 Rank 0 prints ONE JSON line.
 """
@@ -123,7 +129,7 @@ def emit(out):
     print(json.dumps(line, separators=(",", ":")), flush=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="default: two epochs of full batches")
@@ -150,9 +156,14 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=3,
                     help="timed CPU steps at the headline batch (a step of 2M interactions costs the host ~7 s); the "
                          ">= 30 steps of SURVEY 8(d) run at B = 65536 on the same tables")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed regions of --steps steps each on the headline leg; `value` is their median (boxes and "
-                         "passes differ by a few per cent)")
+                         "passes differ by a few per cent; default 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: three timed regions, the secondary, CPU "
+                         "baseline and extra legs, the device copy rate; N>1: replica check, sweeps, one-GPU reference")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-extras", action="store_true",
                     help="N=1: skip the `extra` legs (Zipf ids, Adam, B = 65536, NeuMF at ml-1m shapes, LightGCN at "
                          "Amazon-Book shapes)")
@@ -162,7 +173,10 @@ def parse():
                          "sharding.auto_exchange_slices, from the exchange bytes, an assumed bus rate and the batch)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL; gloo only to exercise the N>1 code path on one GPU)")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    return a
 
 
 def synth_triples(U, I, nnz, seed, device, dist_kind="uniform"):
@@ -274,6 +288,32 @@ def free_data(data):
     torch.cuda.empty_cache()
 
 
+DUMP_BYTES_PER_TABLE = 28 << 20        # two tables + their row ids + the accumulator stay under the 64 MB of --dump-outputs
+
+
+def dump_outputs(dirpath, P, Q, epoch_acc, seed=2022):
+    """--dump-outputs: what the timed steps hand their caller after the last one - the user table P and the item table Q
+    (updated in place) and the epoch accumulator [loss sum, non-finite losses] - as DIR/<name>.npy.  A table larger than
+    28 MB is written as a fixed sample of its rows (drawn from `seed`, independent of the values): DIR/P.npy holds the
+    rows DIR/P_rows.npy lists, likewise Q.  float32 tables, float64 row ids and accumulator: at most 64 MB in all."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for name, T in (("P", P), ("Q", Q)):
+        n, row_bytes = T.shape[0], T.shape[1] * T.element_size()
+        rows = torch.arange(n)
+        if n * row_bytes > DUMP_BYTES_PER_TABLE:
+            rows = torch.randperm(n, generator=g)[:DUMP_BYTES_PER_TABLE // row_bytes].sort().values
+        out[name] = T.detach()[rows.to(T.device)].float().cpu().numpy()
+        out[name + "_rows"] = rows.numpy().astype(np.float64)
+    out["epoch_acc"] = epoch_acc.detach().double().cpu().numpy()
+    assert sum(x.nbytes for x in out.values()) <= 64 << 20
+    for name, x in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), x)
+    return sorted(out)
+
+
 def measure(a, data, rank, world, dev, B, slices, steps, warmup, want_cpu_batches=0, repeats=1, exchange="dense"):
     """warmup + `steps` timed steps of batch size B (per rank) over `data`; max over ranks of the wall time.
     repeats > 1: that many timed regions of `steps` steps, each bracketed like the first; the result is the region
@@ -383,7 +423,7 @@ def measure(a, data, rank, world, dev, B, slices, steps, warmup, want_cpu_batche
            "dt": dt, "lr": lr, "reg": reg, "step_ms": step_ms, "plan_kind": data["plan_kind"], "cpu_batches": cpu_batches,
            "plan_bytes": sum(p.nbytes for p in plans), "index_bytes": index.nbytes if index is not None else 0,
            "staged": trainer.staged if trainer is not None else (a.item_mode == "fused"), "slices": slices,
-           "split_ms": split, "loss_sum": loss_sum, "all_dt": all_dt,
+           "split_ms": split, "loss_sum": loss_sum, "all_dt": all_dt, "epoch_acc": ctx.epoch_acc,
            "wire_bytes": dict(trainer.wire_bytes) if trainer is not None else None}
     ctx.close()
     for p in plans:
@@ -839,7 +879,7 @@ def main():
                 "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}
 
     wl = a.workload if a.workload != "auto" else ("c2" if world == 1 else "c3")
-    want_cpu = a.cpu_steps if (world == 1 and rank == 0 and not a.no_cpu_baseline) else 0
+    want_cpu = a.cpu_steps if (a.full and world == 1 and rank == 0 and not a.no_cpu_baseline) else 0
     B_main = a.batch if a.batch is not None else ((1 << 21) if world == 1 else (1 << 24))
 
     def guarded(what, fn, *args, collective=True):
@@ -863,7 +903,7 @@ def main():
         return res
 
     check = None
-    if world > 1 and not a.no_replica_check and a.item_mode == "fused":
+    if a.full and world > 1 and not a.no_replica_check and a.item_mode == "fused":
         check = guarded("replica_check", replica_check, a, rank, world, dev)
 
     data = build_data(a, rank, world, dev, wl)
@@ -879,9 +919,11 @@ def main():
             r = measure(a, data, rank, world, dev, B_main, 1, a.steps, a.warmup, want_cpu, repeats=a.repeats)
     else:
         r = measure(a, data, rank, world, dev, B_main, a.slices, a.steps, a.warmup, want_cpu, repeats=a.repeats)
+    if a.dump_outputs and rank == 0:       # before any other leg touches the tables
+        dump_outputs(a.dump_outputs, data["P"], data["Q"], r["epoch_acc"])
     # N = 1: the other operating points of SURVEY 8(d) and the other BASELINE configs, on the same JSON line as `extra`
     # (each a guarded leg: an exception lands on the line instead of costing the headline number)
-    want_extras = (world == 1 and wl == "c2" and not a.no_extras and a.item_mode == "fused" and a.batch is None
+    want_extras = (a.full and world == 1 and wl == "c2" and not a.no_extras and a.item_mode == "fused" and a.batch is None
                    and a.nnz is None and a.dist == "uniform")
     extra = {}
     cpu_mid = [None]
@@ -938,7 +980,7 @@ def main():
         watchdog.daemon = True
         watchdog.start()
     sweep = []
-    if world > 1 and wl in ("c3", "tiny") and not a.no_sweep and a.item_mode == "fused" and (a.batch is None or wl == "tiny"):
+    if a.full and world > 1 and wl in ("c3", "tiny") and not a.no_sweep and a.item_mode == "fused" and (a.batch is None or wl == "tiny"):
         # the regimes of DESIGN.md section 5 in one launch: the exchange is a fixed 2 x 231 MB per step and rank, so
         # the batch decides how much compute it is spread over; slices > 1 hides it under the item pass
         # (the tiny workload runs a miniature of the same sweep: it exists to exercise this code on a one-GPU box)
@@ -951,7 +993,7 @@ def main():
                 sweep.append(guarded(f"sweep point B_local={Bl} slices={sl}", measure, a, data, rank, world, dev, Bl, sl,
                                      min(fb, 16), 2))
     xchg = []
-    if world > 1 and wl in ("c3", "tiny") and not a.no_sweep and a.item_mode == "fused" and (a.batch is None or wl == "tiny"):
+    if a.full and world > 1 and wl in ("c3", "tiny") and not a.no_sweep and a.item_mode == "fused" and (a.batch is None or wl == "tiny"):
         # the reference's batch sizes under the sharded step (basic.yaml:23: B = 256 ... 65 536): the dense exchange moves
         # the whole item table for a few thousand touched rows, the touched-rows exchange (sharding.py, round 6) only their
         # union - wire bytes per step and rank of both forms, and the measured step of each (no speed-up claim is made
@@ -969,7 +1011,7 @@ def main():
     free_data(data)
 
     secondary = None
-    if world == 1 and wl == "c2" and not a.no_secondary and a.item_mode == "fused" and a.batch is None and a.nnz is None:
+    if a.full and world == 1 and wl == "c2" and not a.no_secondary and a.item_mode == "fused" and a.batch is None and a.nnz is None:
         d2 = build_data(a, rank, world, dev, "c3", nnz_override=SECONDARY_NNZ)
         r2 = measure(a, d2, rank, world, dev, 1 << 21, 1, None, a.warmup)
         if want_extras:      # Adam where the byte model has no duplicate rows to be generous about: ~1.1 samples per touched user
@@ -1024,7 +1066,7 @@ def main():
         torch.cuda.empty_cache()
 
     ref, ref_global = None, {}
-    if world > 1 and wl in ("c3", "tiny") and not a.no_ref:
+    if a.full and world > 1 and wl in ("c3", "tiny") and not a.no_ref:
         # the same workload on ONE GPU (rank 0; the others wait), so that the N-GPU / 1-GPU ratio on BASELINE configs[2]
         # is on this line - at the single-GPU operating point (2M-interaction steps) AND at the N-GPU run's GLOBAL batch
         # (the loss is a batch sum and one GPU's throughput rises with B: only the second ratio compares like with like)
@@ -1098,7 +1140,7 @@ def main():
                          "algorithmic_bytes_per_interaction": ALGO_BYTES_PER_INTERACTION_SGD(d),
                          "gpu_ms_per_step_events": gpu_ms_mean, "gpu_ms_per_step_median": step_ms[len(step_ms) // 2]},
         }
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             # what this box's HBM delivers to the simplest kernels there are, measured now (outside every timed region): the
             # runtime's device-to-device copy of 2 GiB (bytes read + written).  `peak` stays the guide's 8 TB/s; this says how
             # much of it a copy reaches here (profiles/r06_gather_probe.txt: 5.0 copy / 5.5 read-only / 5.3 write-only)

@@ -22,6 +22,7 @@ and what is run through them:
       -> MF.rank.
   (3) rank_kat.npz    — MF.rank / MF.full_rank on random tables incl. duplicate
       candidates (MFRecommender.py:106-133).
+  (4) get_ur_ir.npz   — get_ur / get_ir (utils.py:19-51) on ml100k train rows.
 """
 import logging
 import os
@@ -271,6 +272,21 @@ def make_rank_kat():
     print("rank_kat.npz: preds", preds.shape, "full", full.shape)
 
 
+def make_get_ur_ir():
+    """(4) get_ur_ir.npz — daisy.utils.utils.get_ur / get_ir (utils.py:19-51) on the first 20 000 train rows of
+    ml100k_c1.npz, as sorted (key, value) pairs: the answer tests/test_host_logic.py holds the mirrors to."""
+    import pandas as pd
+    from daisy.utils.utils import get_ir
+    g = np.load(os.path.join(HERE, "ml100k_c1.npz"))
+    df = pd.DataFrame({"user": g["train_users"][:20000], "item": g["train_items"][:20000], "rating": 1.0})
+
+    def pairs(d):
+        return np.array(sorted((int(k), int(v)) for k, s in d.items() for v in s), dtype=np.int64).reshape(-1, 2)
+
+    np.savez_compressed(os.path.join(HERE, "get_ur_ir.npz"), ur=pairs(get_ur(df)), ir=pairs(get_ir(df)))
+    print("get_ur_ir.npz:", len(get_ur(df)), "users,", len(get_ir(df)), "items")
+
+
 if __name__ == "__main__":  # pragma: no cover
     make_kat_steps()
     make_rank_kat()
@@ -278,3 +294,4 @@ if __name__ == "__main__":  # pragma: no cover
     make_ml100k(out="ml100k_c1_adam.npz", optimizer="adam", lr=0.001)
     make_ml100k(epochs=2, out="ml100k_default.npz", factors=100, num_ng=4)
     make_kat_optimizers()
+    make_get_ur_ir()

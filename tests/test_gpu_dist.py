@@ -163,7 +163,7 @@ def test_bench_self_spawns_its_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "tiny",
-                        "--backend", "gloo", "--batch", "65536", "--steps", "6", "--warmup", "2"],
+                        "--backend", "gloo", "--batch", "65536", "--steps", "6", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])

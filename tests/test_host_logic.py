@@ -69,11 +69,9 @@ def test_ops_reject_host_tensors():
 
 def test_get_ur_get_ir_build_the_reference_dicts(ml100k):
     """utils.py:19-51 without the row loop: same keys, same sets, same container type; on the ml-100k train set and
-    on edge cases (empty frame, duplicate rows, one user).  Where the reference checkout is reachable, its own
-    functions are the judge; everywhere, a literal restatement of its loop."""
-    import importlib
+    on edge cases (empty frame, duplicate rows, one user).  The judges: a literal restatement of its loop, and on the
+    ml-100k rows the reference's own functions' answer, stored in tests/golden/get_ur_ir.npz."""
     import os
-    import sys
     from collections import defaultdict
     import pandas as pd
     from daisyrec_amd.utils.utils import get_ir, get_ur
@@ -92,15 +90,11 @@ def test_get_ur_get_ir_build_the_reference_dicts(ml100k):
         ur, ir = get_ur(df), get_ir(df)
         assert type(ur) is defaultdict and ur == loop(df, "user", "item") and ir == loop(df, "item", "user")
         assert all(type(k) is int for k in ur) and all(type(i) is int for s in ur.values() for i in s)
-    ref = os.environ.get("DAISY_REFERENCE", "/root/reference")
-    if os.path.isdir(os.path.join(ref, "daisy")):
-        sys.path.insert(0, ref)
-        sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden", "_shims"))
-        try:
-            U = importlib.import_module("daisy.utils.utils")
-            assert get_ur(big) == U.get_ur(big) and get_ir(big) == U.get_ir(big)
-        finally:
-            sys.path.remove(ref)
+    # the reference's own functions on `big` (tests/golden/make_golden.py::make_get_ur_ir), as sorted (key, value) pairs
+    want = np.load(os.path.join(os.path.dirname(__file__), "golden", "get_ur_ir.npz"))
+    for have, key in ((get_ur(big), "ur"), (get_ir(big), "ir")):
+        pairs = sorted((k, v) for k, s in have.items() for v in s)
+        np.testing.assert_array_equal(np.array(pairs, dtype=np.int64).reshape(-1, 2), want[key])
 
 
 def test_bench_byte_model_and_roofline_arithmetic():
@@ -123,6 +117,36 @@ def test_bench_byte_model_and_roofline_arithmetic():
     ach8, _ = bench.roofline_of(dict(r, dt=0.0090), 8)                                      # N > 1: per-GPU event time
     assert abs(ach8 - 1548 * B / 0.60e-3 / 1e9) < 1e-6 * ach8
     assert 0.0 < ach / bench.HBM_PEAK_GBS < 1.0
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """bench.py without --full: one timed region of exactly --steps steps (three with --full, --repeats overrides either);
+    dump_outputs: the tables as float32 (a table over 28 MB as a fixed sample of its rows, ids beside it as float64), the
+    accumulator as float64, at most 64 MB in all, the same rows for the same seed whatever the values"""
+    import torch
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.full, a.repeats, a.steps, a.warmup, a.dump_outputs) == (False, 1, 5, 2, None)
+    f = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert f.full and f.repeats == 3 and f.dump_outputs == str(tmp_path)
+    assert bench.parse(["--full", "--repeats", "2"]).repeats == 2 and bench.parse(["--repeats", "2"]).repeats == 2
+    g = torch.Generator().manual_seed(0)
+    P, Q = torch.randn(200_000, 64, generator=g), torch.randn(1000, 64, generator=g)     # P: 51 MB -> sampled
+    acc = torch.tensor([12.5, 0.0], dtype=torch.float64)
+    names = bench.dump_outputs(str(tmp_path / "a"), P, Q, acc)
+    assert names == ["P", "P_rows", "Q", "Q_rows", "epoch_acc"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert sum(x.nbytes for x in got.values()) <= 64 << 20
+    assert got["P"].dtype == np.float32 and got["Q"].dtype == np.float32 and got["epoch_acc"].dtype == np.float64
+    assert got["P_rows"].dtype == np.float64 and got["Q_rows"].dtype == np.float64
+    rows = got["P_rows"].astype(np.int64)
+    assert rows.shape == (bench.DUMP_BYTES_PER_TABLE // 256,) and np.all(np.diff(rows) > 0) and rows[-1] < 200_000
+    np.testing.assert_array_equal(got["P"], P.numpy()[rows])
+    np.testing.assert_array_equal(got["Q_rows"], np.arange(1000))
+    np.testing.assert_array_equal(got["Q"], Q.numpy())
+    np.testing.assert_array_equal(got["epoch_acc"], [12.5, 0.0])
+    bench.dump_outputs(str(tmp_path / "b"), P * 2, Q, acc)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "P_rows.npy"), got["P_rows"])
 
 
 def test_bench_cpu_leg_runs_and_reports_its_three_samples():

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04m
 mkdir -p $O
-timeout 400 python $R/bench.py > $O/bench.json 2> $O/bench.err
+timeout 400 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 C3S="--workload c3 --nnz 100000000"
 for tag in c2 c3s; do
   if [ $tag = c2 ]; then W="--no-secondary"; else W="$C3S"; fi

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r06m
 mkdir -p $O
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 C3S="--workload c3 --nnz 100000000"
 for tag in c2 c3s; do
   if [ $tag = c2 ]; then W="--no-secondary"; else W="$C3S"; fi
