@@ -29,7 +29,8 @@ ST_LOSS_DATA, ST_L1_U, ST_L1_I, ST_L1_J, ST_SQ_U, ST_SQ_I, ST_SQ_J = range(7)
 ST_LOSS, ST_NORM_U, ST_NORM_I, ST_NORM_J = 7, 8, 9, 10
 ST_SUM_COEF = 12
 ST_SQ_U_PRE = 13
-ABI_VERSION = 7
+ABI_VERSION = 8
+NGCF_MAX_WIDTH, NGCF_NODE_STREAM, NGCF_MESS_STREAM = 256, 0x100, 0x200
 
 _p = C.c_void_p
 _i32, _i64, _u64, _f32, _sz = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
@@ -148,6 +149,14 @@ SIGNATURES = {
     "daisy_lgcn_reg_grad": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _p, _p, _p, _p]),
     "daisy_axpby_f32": (C.c_int, [_p, _f32, _f32, _p, _i64, _i32, _p]),
     "daisy_csr_row_sum": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
+    "daisy_lgcn_spmm_ex": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64, _i32, _p]),
+    "daisy_dropout_mask": (C.c_int, [_u64, C.c_uint32, _i64, _f32, _p, _p]),
+    "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
+                                           _i32, _p]),
+    "daisy_ngcf_layer_backward": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i64,
+                                            _i32, _i32, _f32, _u64, _i32, _p]),
+    "daisy_ngcf_wgrad_reduce": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "daisy_csr_workspace_bytes": (_sz, [_i64]),
     "daisy_build_user_csr": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "daisy_sample_neg_per_user": (C.c_int, [_p, _p, _i64, _i64, _i32, _u64, _u64, _p, _p]),

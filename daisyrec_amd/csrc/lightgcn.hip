@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "neumf_internal.h"
 
 namespace daisy {
 
@@ -151,6 +152,107 @@ __global__ __launch_bounds__(kBlock) void k_lg_reg_apply(const float *__restrict
     }
 }
 
+
+// ---- NGCF's products (csrc/ngcf.hip): strided rows, Y += A X, node dropout and the masked transpose ----
+// The rows are cut into segments of at most kSegEntries entries (built once per graph): one wave per segment, its lanes
+// in G = 64 / LPR groups of LPR lanes; group g sums the segment's entries g, g + G, ... in stored order and the groups
+// are combined by a fixed butterfly.  A row of one segment is written directly; the segments of a longer row (popular
+// items: tens of thousands of entries) write partial rows that k_lg_spmm_join adds in segment order.  Nothing depends
+// on timing, so the product is bitwise reproducible.  Entry e scales by keep(e) / (1 - p) (keep(mirror[e]) for the
+// transpose).
+constexpr int kSegEntries = 256;
+struct SpmmSeg {
+    int64_t e0;
+    int32_t len, row, slot;     // slot < 0: the row's only segment, else its partial row in the scratch
+    int32_t pad;
+};
+struct SpmmLong {
+    int32_t row, slot0, nseg;
+};
+
+template <int LPR, bool VEC4>
+__global__ __launch_bounds__(kBlock) void k_lg_spmm_seg(const SpmmSeg *__restrict__ segs, int64_t nsegs,
+                                                        const uint2 *__restrict__ esu, const float2 *__restrict__ coef,
+                                                        const int32_t *__restrict__ mirror,
+                                                        const float *__restrict__ X, int64_t ldx, int d,
+                                                        float *__restrict__ Y, int64_t ldy, float *__restrict__ part,
+                                                        int accumulate, uint32_t thresh, float scale, uint64_t seed) {
+    constexpr int G = kWave / LPR;
+    constexpr int V = VEC4 ? 4 : 1;
+    const int lane = threadIdx.x % kWave, g = lane / LPR, l = lane % LPR;
+    const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;
+    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / kWave);
+    const int nchunk = (d + LPR * V - 1) / (LPR * V);          // column passes (d > LPR * V: scalar rows up to 512)
+    for (int64_t sg = wave; sg < nsegs; sg += nwaves) {
+        const SpmmSeg seg = segs[sg];
+        const int64_t e1 = seg.e0 + seg.len;
+        for (int ch = 0; ch < nchunk; ++ch) {
+            const int c = (ch * LPR + l) * V;
+            const bool in = c < d;
+            float acc[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) acc[v] = 0.f;
+            for (int64_t e = seg.e0 + g; e < e1; e += G) {
+                float w = coef[e].x;
+                if (thresh) w = drop_keep(seed, DAISY_NGCF_NODE_STREAM, mirror ? (uint64_t)mirror[e] : (uint64_t)e, thresh)
+                                    ? w * scale : 0.f;
+                const float *xr = X + (int64_t)esu[e].y * ldx;
+                if (in) {
+                    if constexpr (VEC4) {
+                        const float4 t = *reinterpret_cast<const float4 *>(xr + c);
+                        acc[0] = fmaf(w, t.x, acc[0]); acc[1] = fmaf(w, t.y, acc[1]);
+                        acc[2] = fmaf(w, t.z, acc[2]); acc[3] = fmaf(w, t.w, acc[3]);
+                    } else {
+                        acc[0] = fmaf(w, xr[c], acc[0]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int off = LPR; off < kWave; off <<= 1)
+#pragma unroll
+                for (int v = 0; v < V; ++v) acc[v] += __shfl_xor(acc[v], off);
+            if (g == 0 && in) {
+                if (seg.slot >= 0) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v) part[(int64_t)seg.slot * d + c + v] = acc[v];
+                    continue;
+                }
+                float *yr = Y + (int64_t)seg.row * ldy + c;
+#pragma unroll
+                for (int v = 0; v < V; ++v) yr[v] = accumulate ? yr[v] + acc[v] : acc[v];
+            }
+        }
+    }
+}
+
+// the rows of more than one segment: Y[row] (+)= sum of their partial rows in segment order
+__global__ void k_lg_spmm_join(const SpmmLong *__restrict__ rows, int64_t nrows, const float *__restrict__ part, int d,
+                               float *__restrict__ Y, int64_t ldy, int accumulate) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nrows * d; t += (int64_t)gridDim.x * blockDim.x) {
+        const SpmmLong r = rows[t / d];
+        const int c = (int)(t % d);
+        float s = 0.f;
+        for (int q = 0; q < r.nseg; ++q) s += part[(int64_t)(r.slot0 + q) * d + c];
+        float *y = Y + (int64_t)r.row * ldy + c;
+        *y = accumulate ? *y + s : s;
+    }
+}
+
+// mirror[e] = the entry (c, r) of entry e = (r, c): binary search of r among row c's columns (ascending)
+__global__ void k_lg_mirror(const uint32_t *__restrict__ ekey, const uint2 *__restrict__ esu,
+                            const int64_t *__restrict__ row_ptr, int64_t nnz, int32_t *__restrict__ mirror) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = ekey[e] >> 1, c = esu[e].y;
+        int64_t lo = row_ptr[c], hi = row_ptr[c + 1];
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (esu[mid].y < r) lo = mid + 1;
+            else hi = mid;
+        }
+        mirror[e] = (int32_t)lo;
+    }
+}
+
 }  // namespace daisy
 
 using namespace daisy;
@@ -168,6 +270,12 @@ struct daisy_lgcn_graph {
     float *edge_vec, *edge_b;
     int32_t *edge_item, *edge_whole;
     int64_t *row_ptr_host;   // [N+1] first entry of every row (lazy: daisy_lgcn_spmm_rows)
+    int64_t *row_ptr_dev;    // the same on the device (lazy: daisy_lgcn_spmm_ex)
+    int32_t *mirror;         // [nnz] entry (c, r) of entry (r, c) (lazy: first masked transpose)
+    SpmmSeg *segs;           // daisy_lgcn_spmm_ex's row segments and the rows of several segments (lazy)
+    SpmmLong *long_rows;
+    float *seg_part;         // [partial rows][kMaxD] scratch
+    int64_t nsegs, nlong, nslots;
 };
 
 // row_ptr[r] = first entry e with ekey[e] >= r << 1
@@ -246,6 +354,10 @@ int daisy_lgcn_graph_create(daisy_lgcn_graph **out, const int32_t *users, const 
     g->reproducible = 0;
     g->edge_arena = nullptr; g->edge_d = 0;
     g->row_ptr_host = nullptr;
+    g->row_ptr_dev = nullptr;
+    g->mirror = nullptr;
+    g->segs = nullptr; g->long_rows = nullptr; g->seg_part = nullptr;
+    g->nsegs = g->nlong = g->nslots = 0;
     size_t goff = 0;
     auto gtake = [&](size_t bytes) { size_t o = goff; goff += align_up(bytes); return o; };
     const size_t g_k = gtake((size_t)g->nnz * 4), g_s = gtake((size_t)g->nnz * 8), g_c = gtake((size_t)g->nnz * 8);
@@ -279,6 +391,11 @@ int daisy_lgcn_graph_destroy(daisy_lgcn_graph *g) {
     if (g->arena) (void)hipFree(g->arena);
     if (g->edge_arena) (void)hipFree(g->edge_arena);
     if (g->row_ptr_host) free(g->row_ptr_host);
+    if (g->row_ptr_dev) (void)hipFree(g->row_ptr_dev);
+    if (g->mirror) (void)hipFree(g->mirror);
+    if (g->segs) (void)hipFree(g->segs);
+    if (g->long_rows) (void)hipFree(g->long_rows);
+    if (g->seg_part) (void)hipFree(g->seg_part);
     delete g;
     return DAISY_OK;
 }
@@ -369,6 +486,89 @@ int daisy_lgcn_spmm_rows(const daisy_lgcn_graph *g, const float *X, float *Yrows
     if (rc) return rc;
     return segsum_rows(X, g->coef, g->ekey + e_lo, g->esu + e_lo, e_hi - e_lo, d, base, gm->edge_vec, gm->edge_item,
                        gm->edge_b, gm->edge_whole, s);
+}
+
+int daisy_lgcn_spmm_ex(const daisy_lgcn_graph *g, const float *X, int64_t ldx, float *Y, int64_t ldy, int32_t d,
+                       int32_t accumulate, float node_p, uint64_t seed, int32_t transpose, daisy_stream_t stream) {
+    DAISY_CHECK_ARG(g && X && Y && X != Y, "lgcn_spmm_ex: NULL or aliased argument");
+    DAISY_CHECK_ARG(d >= 1 && d <= kMaxD && ldx >= d && ldy >= d, "lgcn_spmm_ex: d=%d ldx=%lld ldy=%lld out of range",
+                    (int)d, (long long)ldx, (long long)ldy);
+    DAISY_CHECK_ARG(node_p >= 0.f && node_p < 1.f, "lgcn_spmm_ex: node_p=%g outside [0, 1)", (double)node_p);
+    hipStream_t s = LS(stream);
+    const int64_t N = g->U + g->I;
+    daisy_lgcn_graph *gm = const_cast<daisy_lgcn_graph *>(g);      // caches only: the matrix is untouched
+    if (!gm->segs) {                  // once: row offsets and the row segments (one host synchronisation)
+        DAISY_HIP(hipMalloc((void **)&gm->row_ptr_dev, (size_t)(N + 1) * 8));
+        hipLaunchKernelGGL(k_lg_row_ptr, dim3(grid_for(N + 1, kBlock)), dim3(kBlock), 0, s, g->ekey, g->nnz, N,
+                           gm->row_ptr_dev);
+        DAISY_LAUNCH_CHECK();
+        int64_t *rp = (int64_t *)malloc((size_t)(N + 1) * 8);
+        hipError_t e = hipMemcpyAsync(rp, gm->row_ptr_dev, (size_t)(N + 1) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            free(rp);
+            set_error("lgcn_spmm_ex: reading the row offsets failed: %s", hipGetErrorString(e));
+            return DAISY_ERR_HIP;
+        }
+        int64_t nseg = 0, nlong = 0;
+        for (int64_t r = 0; r < N; ++r) {
+            const int64_t k = (rp[r + 1] - rp[r] + kSegEntries - 1) / kSegEntries;
+            nseg += k > 1 ? k : 1;
+            nlong += k > 1;
+        }
+        SpmmSeg *hs = (SpmmSeg *)malloc((size_t)nseg * sizeof(SpmmSeg));
+        SpmmLong *hl = (SpmmLong *)malloc((size_t)(nlong > 0 ? nlong : 1) * sizeof(SpmmLong));
+        int64_t is = 0, il = 0, slot = 0;
+        for (int64_t r = 0; r < N; ++r) {
+            const int64_t len = rp[r + 1] - rp[r], k = (len + kSegEntries - 1) / kSegEntries;
+            if (k <= 1) { hs[is++] = SpmmSeg{rp[r], (int32_t)len, (int32_t)r, -1, 0}; continue; }
+            hl[il++] = SpmmLong{(int32_t)r, (int32_t)slot, (int32_t)k};
+            for (int64_t q = 0; q < k; ++q) {
+                const int64_t e0 = rp[r] + q * kSegEntries;
+                const int64_t n = (len - q * kSegEntries) < kSegEntries ? len - q * kSegEntries : kSegEntries;
+                hs[is++] = SpmmSeg{e0, (int32_t)n, (int32_t)r, (int32_t)slot++, 0};
+            }
+        }
+        free(rp);
+        e = hipMalloc((void **)&gm->segs, (size_t)nseg * sizeof(SpmmSeg));
+        if (e == hipSuccess) e = hipMalloc((void **)&gm->long_rows, (size_t)(nlong > 0 ? nlong : 1) * sizeof(SpmmLong));
+        if (e == hipSuccess) e = hipMalloc((void **)&gm->seg_part, (size_t)(slot > 0 ? slot : 1) * kMaxD * 4);
+        if (e == hipSuccess) e = hipMemcpy(gm->segs, hs, (size_t)nseg * sizeof(SpmmSeg), hipMemcpyHostToDevice);
+        if (e == hipSuccess && nlong > 0) e = hipMemcpy(gm->long_rows, hl, (size_t)nlong * sizeof(SpmmLong), hipMemcpyHostToDevice);
+        free(hs);
+        free(hl);
+        if (e != hipSuccess) {
+            set_error("lgcn_spmm_ex: segment table: %s", hipGetErrorString(e));
+            return DAISY_ERR_HIP;
+        }
+        gm->nsegs = nseg; gm->nlong = nlong; gm->nslots = slot;
+    }
+    const uint32_t thresh = keep_threshold(node_p);
+    const float scale = thresh ? 1.f / (1.f - node_p) : 1.f;
+    if (thresh && transpose && !gm->mirror) {
+        DAISY_HIP(hipMalloc((void **)&gm->mirror, (size_t)(g->nnz > 0 ? g->nnz : 1) * 4));
+        if (g->nnz > 0)
+            hipLaunchKernelGGL(k_lg_mirror, dim3(grid_for(g->nnz, kBlock)), dim3(kBlock), 0, s, g->ekey, g->esu,
+                               gm->row_ptr_dev, g->nnz, gm->mirror);
+        DAISY_LAUNCH_CHECK();
+    }
+    const int32_t *mir = (thresh && transpose) ? gm->mirror : nullptr;
+    const bool vec = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 15) == 0;
+    const dim3 grid(grid_for(gm->nsegs, kBlock / kWave, kMaxGridSparse)), block(kBlock);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, 0, s, gm->segs, gm->nsegs, g->esu, g->coef, mir, X, ldx, (int)d, Y, ldy,
+                           gm->seg_part, (int)accumulate, thresh, scale, seed);
+    };
+    if (!vec) go(k_lg_spmm_seg<kWave, false>);
+    else if (d <= 32) go(k_lg_spmm_seg<8, true>);
+    else if (d <= 64) go(k_lg_spmm_seg<16, true>);
+    else if (d <= 128) go(k_lg_spmm_seg<32, true>);
+    else go(k_lg_spmm_seg<64, true>);
+    if (gm->nlong > 0)
+        hipLaunchKernelGGL(k_lg_spmm_join, dim3(grid_for(gm->nlong * d, kBlock)), dim3(kBlock), 0, s, gm->long_rows,
+                           gm->nlong, gm->seg_part, (int)d, Y, ldy, (int)accumulate);
+    DAISY_LAUNCH_CHECK();
+    return DAISY_OK;
 }
 
 int daisy_lgcn_propagate(const daisy_lgcn_graph *g, const float *E0, int32_t d, int32_t num_layers,

@@ -59,6 +59,13 @@ __host__ __device__ __forceinline__ bool drop_keep(uint64_t seed, uint32_t strea
     return h >= thresh;
 }
 
+// the threshold of drop_keep for dropout probability p (0: dropout off - every element kept)
+inline uint32_t keep_threshold(float p) {
+    if (!(p > 0.f)) return 0u;
+    const double t = (double)p * 4294967296.0;
+    return (t >= 4294967295.0) ? 4294967295u : (uint32_t)t;
+}
+
 // the three pair layouts of daisy_neumf_scores plus the training batch
 struct PairSrc {
     const int32_t *u, *i, *j;     // training: row r < B -> (u[r], i[r]); r >= B -> (u[r-B], j[r-B])

@@ -15,6 +15,11 @@
 //   torch.ops.daisyrec.bpr_mf_step(P, Q, u, i, j, lr, reg_1, reg_2, gamma, loss_type)
 //                                                                           daisy_bpr_set_batch + daisy_bpr_sgd_step
 //                                                                           AbstractRecommender.py:119-128
+//   torch.ops.daisyrec.ngcf_layer_fwd(E, X, W1, b1, W2, b2, mess_p, seed, layer) -> (Y, norm)
+//                                                                           daisy_ngcf_layer_forward  NGCFRecommender.py:38-60,163-167
+//   torch.ops.daisyrec.ngcf_layer_bwd(dY, Y, norm, E, X, W1, W2, mess_p, seed, layer) -> (dE, dX, dW1, db1, dW2, db2)
+//                                                                           daisy_ngcf_layer_backward + daisy_ngcf_wgrad_reduce
+//                                                                           (dE without A_hat^T dX: the caller's sparse product)
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -148,6 +153,52 @@ at::Tensor bpr_mf_step(at::Tensor P, at::Tensor Q, const at::Tensor &u, const at
     return loss;
 }
 
+std::tuple<at::Tensor, at::Tensor> ngcf_layer_fwd(const at::Tensor &E, const at::Tensor &X, const at::Tensor &W1,
+                                                  const at::Tensor &b1, const at::Tensor &W2, const at::Tensor &b2,
+                                                  double mess_p, int64_t seed, int64_t layer) {
+    for (auto *t : {&E, &X, &W1, &b1, &W2, &b2}) need(*t, at::kFloat, "ngcf_layer_fwd");
+    TORCH_CHECK(E.dim() == 2 && X.sizes() == E.sizes() && W1.dim() == 2 && W1.sizes() == W2.sizes() &&
+                    W1.size(1) == E.size(1) && b1.numel() == W1.size(0) && b2.numel() == W1.size(0),
+                "ngcf_layer_fwd: shapes");
+    same_device(E, {&X, &W1, &b1, &W2, &b2}, "ngcf_layer_fwd");
+    const c10::OptionalDeviceGuard guard(E.device());
+    at::Tensor Y = at::empty({E.size(0), W1.size(0)}, E.options());
+    at::Tensor norm = at::empty({E.size(0)}, E.options());
+    ok(daisy_ngcf_layer_forward(E.data_ptr<float>(), E.size(1), X.data_ptr<float>(), W1.data_ptr<float>(),
+                                b1.data_ptr<float>(), W2.data_ptr<float>(), b2.data_ptr<float>(), Y.data_ptr<float>(),
+                                Y.size(1), norm.data_ptr<float>(), E.size(0), (int32_t)E.size(1), (int32_t)Y.size(1),
+                                (float)mess_p, (uint64_t)seed, (int32_t)layer, stream_of(E)));
+    return {Y, norm};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> ngcf_layer_bwd(
+    const at::Tensor &dY, const at::Tensor &Y, const at::Tensor &norm, const at::Tensor &E, const at::Tensor &X,
+    const at::Tensor &W1, const at::Tensor &W2, double mess_p, int64_t seed, int64_t layer) {
+    for (auto *t : {&dY, &Y, &norm, &E, &X, &W1, &W2}) need(*t, at::kFloat, "ngcf_layer_bwd");
+    TORCH_CHECK(E.dim() == 2 && X.sizes() == E.sizes() && W1.dim() == 2 && W1.sizes() == W2.sizes() &&
+                    W1.size(1) == E.size(1) && Y.dim() == 2 && Y.size(0) == E.size(0) && Y.size(1) == W1.size(0) &&
+                    dY.sizes() == Y.sizes() && norm.numel() == E.size(0),
+                "ngcf_layer_bwd: shapes");
+    same_device(E, {&dY, &Y, &norm, &X, &W1, &W2}, "ngcf_layer_bwd");
+    const c10::OptionalDeviceGuard guard(E.device());
+    const int64_t n = E.size(0);
+    const int32_t din = (int32_t)E.size(1), dout = (int32_t)Y.size(1);
+    at::Tensor dE = at::empty_like(E), dX = at::empty_like(E);
+    at::Tensor dW1 = at::zeros_like(W1), dW2 = at::zeros_like(W2);
+    at::Tensor db1 = at::zeros({dout}, E.options()), db2 = at::zeros({dout}, E.options());
+    const size_t wsb = daisy_ngcf_ws_bytes(n, din, dout);
+    TORCH_CHECK(wsb > 0, "ngcf_layer_bwd: unsupported widths ", din, " -> ", dout);
+    at::Tensor ws = at::empty({(int64_t)wsb}, E.options().dtype(at::kByte));
+    daisy_stream_t s = stream_of(E);
+    ok(daisy_ngcf_layer_backward(dY.data_ptr<float>(), dout, Y.data_ptr<float>(), dout, norm.data_ptr<float>(),
+                                 E.data_ptr<float>(), din, X.data_ptr<float>(), W1.data_ptr<float>(), W2.data_ptr<float>(),
+                                 nullptr, 0, dE.data_ptr<float>(), dX.data_ptr<float>(), (float *)ws.data_ptr(), n, din,
+                                 dout, (float)mess_p, (uint64_t)seed, (int32_t)layer, s));
+    ok(daisy_ngcf_wgrad_reduce((const float *)ws.data_ptr(), n, din, dout, dW1.data_ptr<float>(), db1.data_ptr<float>(),
+                               dW2.data_ptr<float>(), db2.data_ptr<float>(), s));
+    return {dE, dX, dW1, db1, dW2, db2};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(daisyrec, m) {
@@ -157,6 +208,10 @@ TORCH_LIBRARY(daisyrec, m) {
     m.def("sample_uniform_neg(Tensor indptr, Tensor items, int item_num, int num_ng, int seed, int epoch) -> Tensor");
     m.def("bpr_mf_step(Tensor(a!) P, Tensor(b!) Q, Tensor u, Tensor i, Tensor j, float lr, float reg_1, float reg_2, "
           "float gamma, int loss_type) -> Tensor");
+    m.def("ngcf_layer_fwd(Tensor E, Tensor X, Tensor W1, Tensor b1, Tensor W2, Tensor b2, float mess_p, int seed, "
+          "int layer) -> (Tensor, Tensor)");
+    m.def("ngcf_layer_bwd(Tensor dY, Tensor Y, Tensor norm, Tensor E, Tensor X, Tensor W1, Tensor W2, float mess_p, "
+          "int seed, int layer) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP key of a ROCm build
@@ -165,4 +220,6 @@ TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP
     m.impl("mf_full_rank", &mf_full_rank);
     m.impl("sample_uniform_neg", &sample_uniform_neg);
     m.impl("bpr_mf_step", &bpr_mf_step);
+    m.impl("ngcf_layer_fwd", &ngcf_layer_fwd);
+    m.impl("ngcf_layer_bwd", &ngcf_layer_bwd);
 }

@@ -36,6 +36,12 @@ def install(sampler=False, front_end=False):
         ref_lg.LightGCN = LightGCN
     except ImportError:
         pass
+    from .model.NGCFRecommender import NGCF
+    try:                                   # the reference module imports scipy as well
+        ref_ng = importlib.import_module("daisy.model.NGCFRecommender")
+        ref_ng.NGCF = NGCF
+    except ImportError:
+        pass
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -49,6 +49,21 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _rows(t, name):
+    """(pointer, row pitch) of a 2-D float32 device tensor whose rows are contiguous: a whole matrix or a column
+    slice of a wider one (NGCF's concat buffer)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise TypeError(f"{name}: expected a 2-D torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; the HIP path needs device memory "
+                           "(there is no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected dtype torch.float32, got {t.dtype}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: rows must be contiguous")
+    return C.c_void_p(t.data_ptr()), max(int(t.stride(0)), int(t.shape[1]))
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
@@ -1004,7 +1019,13 @@ class LgcnGraph:
             self._work = torch.empty(2 * self.N * d, dtype=torch.float32, device=self.device)
         return self._work
 
-    def spmm(self, X):
+    def spmm(self, X, pitch=None, accumulate=False, keep=None, out=None, transpose=False):
+        """Y = A_hat X.  Any of the NGCF options - a column-slice view X / out (pitch: the rows' stride, taken from the
+        views), accumulate (out += A_hat X), keep=(p, seed) node dropout, transpose - goes through spmm_ex."""
+        if pitch is not None or accumulate or keep is not None or out is not None or transpose:
+            if pitch is not None:
+                assert X.stride(0) == pitch, (X.stride(), pitch)
+            return self.spmm_ex(X, out=out, accumulate=accumulate, keep=keep, transpose=transpose)
         Y = torch.empty_like(X)
         check(lib.daisy_lgcn_spmm(self._h, _ptr(X, torch.float32, "X"), _ptr(Y, torch.float32, "Y"), X.shape[1],
                                   _stream()))
@@ -1017,6 +1038,21 @@ class LgcnGraph:
         check(lib.daisy_lgcn_spmm_rows(self._h, _ptr(X, torch.float32, "X"), _ptr(Yrows[1:], torch.float32, "Yrows"),
                                        X.shape[1], int(row_lo), int(row_hi), _stream()))
         return Yrows[1:1 + row_hi - row_lo]
+
+    def spmm_ex(self, X, out=None, accumulate=False, keep=None, transpose=False):
+        """NGCF's product: out (=, or += with accumulate) A_hat X, where X and out may be column slices of wider
+        buffers (rows contiguous; the row pitch is their stride).  keep=(p, seed): node dropout of the stored entries
+        (NGCFRecommender.py:19-36), transpose: the masked matrix's transpose.  Bitwise reproducible."""
+        if out is None:
+            out = torch.zeros(X.shape[0], X.shape[1], dtype=torch.float32, device=X.device) if accumulate else \
+                torch.empty(X.shape[0], X.shape[1], dtype=torch.float32, device=X.device)
+        assert X.shape[0] == self.N and out.shape == X.shape, (X.shape, out.shape, self.N)
+        p, seed = keep if keep is not None else (0.0, 0)
+        xp, ldx = _rows(X, "X")
+        yp, ldy = _rows(out, "out")
+        check(lib.daisy_lgcn_spmm_ex(self._h, xp, ldx, yp, ldy, X.shape[1], int(bool(accumulate)), float(p),
+                                     int(seed) & (2 ** 64 - 1), int(bool(transpose)), _stream()))
+        return out
 
     def propagate(self, E0, num_layers, out=None):
         """LightGCN.forward (LightGCNRecommender.py:117-129): mean_k A_hat^k E0, [N, d]."""
@@ -1059,3 +1095,56 @@ def csr_row_sum(indptr, cols, X, out):
     check(lib.daisy_csr_row_sum(_ptr(indptr, torch.int64, "indptr"), _ptr(cols, torch.int32, "cols"),
                                 _ptr(X, torch.float32, "X"), indptr.numel() - 1, X.shape[1],
                                 _ptr(out, torch.float32, "out"), _stream()))
+
+
+# ---- NGCF (csrc/ngcf.hip; NGCFRecommender.py:38-172) ------------------------------------------------------------------
+NGCF_MAX_WIDTH, NGCF_NODE_STREAM, NGCF_MESS_STREAM = N.NGCF_MAX_WIDTH, N.NGCF_NODE_STREAM, N.NGCF_MESS_STREAM
+
+
+def dropout_mask(seed, stream_id, n, p, device="cuda"):
+    """uint8[n] keep bits of dropout stream `stream_id` (the test hook of the device masks)."""
+    out = torch.empty(int(n), dtype=torch.uint8, device=device)
+    check(lib.daisy_dropout_mask(int(seed) & (2 ** 64 - 1), int(stream_id), int(n), float(p),
+                                 _ptr(out, torch.uint8, "out"), _stream()))
+    return out
+
+
+def ngcf_ws_bytes(n, d_in, d_out):
+    return int(lib.daisy_ngcf_ws_bytes(int(n), int(d_in), int(d_out)))
+
+
+def ngcf_layer_forward(E, X, W1, b1, W2, b2, Y, norm, mess_p=0.0, seed=0, layer=0):
+    """One BiGNN layer + LeakyReLU + message dropout + F.normalize (NGCFRecommender.py:38-60,163-167): Y and norm are
+    written.  E ([N, d_in]) and Y ([N, d_out]) may be column slices of the concat buffer; X = A_hat_drop E."""
+    n, d_in = E.shape
+    d_out = Y.shape[1]
+    ep, lde = _rows(E, "E")
+    yp, ldy = _rows(Y, "Y")
+    check(lib.daisy_ngcf_layer_forward(ep, lde, _ptr(X, torch.float32, "X"), _ptr(W1, torch.float32, "W1"),
+                                       _ptr(b1, torch.float32, "b1"), _ptr(W2, torch.float32, "W2"),
+                                       _ptr(b2, torch.float32, "b2"), yp, ldy, _ptr(norm, torch.float32, "norm"), n,
+                                       d_in, d_out, float(mess_p), int(seed) & (2 ** 64 - 1), int(layer), _stream()))
+    return Y
+
+
+def ngcf_layer_backward(dY, Y, norm, E, X, W1, W2, dE, dX, ws, mess_p=0.0, seed=0, layer=0, gprev=None):
+    """The layer's backward pass: dE = gprev + dS + dT * X, dX = dS + dT * E (the caller adds A_hat_drop^T dX to dE)
+    and the weight-gradient partials in ws (uint8 or float32 of ngcf_ws_bytes; ngcf_wgrad_reduce sums them)."""
+    n, d_in = E.shape
+    d_out = Y.shape[1]
+    dp, ldd = _rows(dY, "dY")
+    yp, ldy = _rows(Y, "Y")
+    ep, lde = _rows(E, "E")
+    gp, ldg = _rows(gprev, "gprev") if gprev is not None else (None, 0)
+    check(lib.daisy_ngcf_layer_backward(dp, ldd, yp, ldy, _ptr(norm, torch.float32, "norm"), ep, lde,
+                                        _ptr(X, torch.float32, "X"), _ptr(W1, torch.float32, "W1"),
+                                        _ptr(W2, torch.float32, "W2"), gp, ldg, _ptr(dE, torch.float32, "dE"),
+                                        _ptr(dX, torch.float32, "dX"), C.c_void_p(ws.data_ptr()), n, d_in, d_out,
+                                        float(mess_p), int(seed) & (2 ** 64 - 1), int(layer), _stream()))
+
+
+def ngcf_wgrad_reduce(ws, n, d_in, d_out, dW1, db1, dW2, db2):
+    """dW1, dW2, db1, db2 += the backward pass's partials, summed in a fixed order."""
+    check(lib.daisy_ngcf_wgrad_reduce(C.c_void_p(ws.data_ptr()), int(n), int(d_in), int(d_out),
+                                      _ptr(dW1, torch.float32, "dW1"), _ptr(db1, torch.float32, "db1"),
+                                      _ptr(dW2, torch.float32, "dW2"), _ptr(db2, torch.float32, "db2"), _stream()))

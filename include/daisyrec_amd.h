@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DAISY_ABI_VERSION 7
+#define DAISY_ABI_VERSION 8
 
 typedef void *daisy_stream_t; /* hipStream_t */
 
@@ -655,6 +655,56 @@ int daisy_lgcn_reg_grad(const float *E0, const int32_t *u, const int32_t *i, con
                         int64_t user_num, int64_t item_num, int32_t d, int32_t pointwise, float reg_1,
                         float reg_2, const double *stats, int32_t *count_ws, float *dE0,
                         daisy_stream_t stream);
+
+/* -------------------------------------------------------------------------
+ * NGCF (daisy/model/NGCFRecommender.py:62-252): the LightGCN adjacency A_hat plus one dense bi-interaction
+ * layer per hidden width.  Layer k maps E = E^{k-1} [N, d_in] to E^k [N, d_out]:
+ *   X   = A_hat_drop E                                        daisy_lgcn_spmm_ex (node dropout: A_hat_drop)
+ *   Z   = (E + X) W1^T + b1 + (X * E) W2^T + b2               one GEMM, K = 2 d_in: [S | T] [W1 | W2]^T
+ *   Y   = normalize(dropout_p(LeakyReLU_0.2(Z)))              row L2 norm, clamp 1e-12 (F.normalize)
+ * E and Y are column slices of the concat buffer out = [E^0 | E^1 | ... | E^L] (row pitches lde / ldy).  Widths
+ * d_in, d_out are 1..DAISY_NGCF_MAX_WIDTH.  W1, W2 are nn.Linear weights [d_out][d_in], b1, b2 [d_out].
+ * Dropout keep bits are a counter hash of (seed, stream, index): message dropout of layer k uses stream
+ * DAISY_NGCF_MESS_STREAM + k and index r * d_out + c; node dropout uses DAISY_NGCF_NODE_STREAM and the index
+ * of the stored entry of A_hat (daisy_lgcn_graph_read order).  Kept values are scaled by 1 / (1 - p).
+ * ---------------------------------------------------------------------- */
+#define DAISY_NGCF_MAX_WIDTH 256
+#define DAISY_NGCF_NODE_STREAM 0x100u
+#define DAISY_NGCF_MESS_STREAM 0x200u
+/* Y = A_hat_drop X (or its transpose), X and Y f32 row slices of pitch ldx / ldy (>= d), d in 1..512, X and Y
+ * distinct.  accumulate != 0: Y += instead of Y =.  node_p in [0, 1): node dropout of the stored entries
+ * (seed as above; 0: A_hat itself).  transpose != 0: A_hat_drop^T - the same entries with the keep bit of
+ * each entry's mirror (A_hat is symmetric, the masked matrix is not).  Row-owner kernel: every row is summed
+ * in a fixed order (rows longer than 256 entries in segments whose partial sums are added in segment order), so the
+ * result is bitwise reproducible.  The first call builds the row segments (one host synchronisation), the first
+ * masked transpose the mirror permutation; both are kept with the graph. */
+int daisy_lgcn_spmm_ex(const daisy_lgcn_graph *g, const float *X, int64_t ldx, float *Y, int64_t ldy, int32_t d,
+                       int32_t accumulate, float node_p, uint64_t seed, int32_t transpose, daisy_stream_t stream);
+/* out[e] = keep bit (1 / 0) of index e < n of dropout stream `stream_id` at probability p in [0, 1) (test hook) */
+int daisy_dropout_mask(uint64_t seed, uint32_t stream_id, int64_t n, float p, uint8_t *out, daisy_stream_t stream);
+/* bytes of the workspace of daisy_ngcf_layer_backward (dZ and the per-workgroup weight-gradient partials) */
+size_t daisy_ngcf_ws_bytes(int64_t n, int32_t d_in, int32_t d_out);
+/* forward of layer `layer` (0-based) over n rows: Y (pitch ldy) and norm[n] = |dropout(LeakyReLU(Z))| per row.
+ * X: f32[n, d_in] contiguous (saved for the backward pass). */
+int daisy_ngcf_layer_forward(const float *E, int64_t lde, const float *X, const float *W1, const float *b1,
+                             const float *W2, const float *b2, float *Y, int64_t ldy, float *norm, int64_t n,
+                             int32_t d_in, int32_t d_out, float mess_p, uint64_t seed, int32_t layer,
+                             daisy_stream_t stream);
+/* backward of the same layer, given dY = dL/dY (pitch ldd) and the forward's Y, norm, E, X:
+ *   dZ           = LeakyReLU' * dropout' * normalize'(dY)
+ *   [dS | dT]    = dZ [W1 | W2]
+ *   dE[n, d_in]  = gprev + dS + dT * X        (gprev: pitch ldg, NULL for 0; dE contiguous)
+ *   dX[n, d_in]  = dS + dT * E                (the caller adds A_hat_drop^T dX to dE: daisy_lgcn_spmm_ex)
+ * and the per-workgroup partials of dW = dZ^T [S | T], db = sum dZ into ws (daisy_ngcf_ws_bytes). */
+int daisy_ngcf_layer_backward(const float *dY, int64_t ldd, const float *Y, int64_t ldy, const float *norm,
+                              const float *E, int64_t lde, const float *X, const float *W1, const float *W2,
+                              const float *gprev, int64_t ldg, float *dE, float *dX, float *ws, int64_t n,
+                              int32_t d_in, int32_t d_out, float mess_p, uint64_t seed, int32_t layer,
+                              daisy_stream_t stream);
+/* dW1, dW2 [d_out][d_in] and db1, db2 [d_out] += the partials of ws summed in a fixed order (no float atomics:
+ * bitwise repeatable).  db1 and db2 receive the same sum (Z = ... + b1 + b2). */
+int daisy_ngcf_wgrad_reduce(const float *ws, int64_t n, int32_t d_in, int32_t d_out, float *dW1, float *db1,
+                            float *dW2, float *db2, daisy_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Item2Vec (rest of SURVEY.md §8f rank 4; daisy/model/Item2VecRecommender.py:15-112).
