@@ -48,6 +48,29 @@ class NeumfParams(C.Structure):
 
 _pp = C.POINTER(NeumfParams)
 
+NFM_MAX_LAYERS, NFM_MAX_FACTORS, NFM_DROP_STREAM, NFM_SMALL_MAX_B = 8, 256, 0x300, 256
+NFM_PATHS = {"auto": 0, "small": 1, "layered": 2}
+NFM_ACT = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
+NFST_LOSS, NFST_LOSS_SUM, NFST_LOSS_DATA, NFST_NORM_U, NFST_NORM_I, NFST_NORM_J, NFST_NONFINITE = range(7)
+NFM_STATS_LEN = 8
+
+
+class NfmParams(C.Structure):
+    """daisy_nfm_params: table of device pointers (include/daisyrec_amd.h)."""
+    _fields_ = [("P", _p), ("Q", _p), ("ub", _p), ("ib", _p), ("bias", _p),
+                ("bn_w", _p * (NFM_MAX_LAYERS + 1)), ("bn_b", _p * (NFM_MAX_LAYERS + 1)),
+                ("W", _p * NFM_MAX_LAYERS), ("b", _p * NFM_MAX_LAYERS), ("wp", _p)]
+
+
+class NfmBnState(C.Structure):
+    """daisy_nfm_bn_state: the BatchNorm buffers of every stage."""
+    _fields_ = [("mean", _p * (NFM_MAX_LAYERS + 1)), ("var", _p * (NFM_MAX_LAYERS + 1)),
+                ("nbt", _p * (NFM_MAX_LAYERS + 1))]
+
+
+_np = C.POINTER(NfmParams)
+_nb = C.POINTER(NfmBnState)
+
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
     "daisy_last_error": (C.c_char_p, []),
@@ -151,6 +174,14 @@ SIGNATURES = {
     "daisy_csr_row_sum": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
     "daisy_lgcn_spmm_ex": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64, _i32, _p]),
     "daisy_dropout_mask": (C.c_int, [_u64, C.c_uint32, _i64, _f32, _p, _p]),
+    "daisy_nfm_ctx_create": (C.c_int, [C.POINTER(_p), _i64, _i32, _i32, _i32, _i32, _i64, _i64]),
+    "daisy_nfm_ctx_destroy": (C.c_int, [_p]),
+    "daisy_nfm_ctx_bytes": (_sz, [_p]),
+    "daisy_nfm_ctx_set_path": (C.c_int, [_p, _i32]),
+    "daisy_nfm_step_grads": (C.c_int, [_p, _np, _np, _nb, _p, _p, _p, _i64, _i32, _f32, _f32, _f32, _f32, _u64, _p, _p]),
+    "daisy_nfm_fit_epoch": (C.c_int, [_p, _np, _np, _nb, _p, _p, _p, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _u64,
+                                      _i64, _i64, _i32, _f32, _p, _p, _p, _p, _i64, _p, _p]),
+    "daisy_nfm_scores": (C.c_int, [_p, _np, _nb, _p, _p, _i64, _i64, _i32, _f32, _u64, _p, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

@@ -20,6 +20,8 @@
 //   torch.ops.daisyrec.ngcf_layer_bwd(dY, Y, norm, E, X, W1, W2, mess_p, seed, layer) -> (dE, dX, dW1, db1, dW2, db2)
 //                                                                           daisy_ngcf_layer_backward + daisy_ngcf_wgrad_reduce
 //                                                                           (dE without A_hat^T dX: the caller's sparse product)
+//   torch.ops.daisyrec.nfm_scores(P, Q, ub, ib, bias, wp, W, b, bn_w, bn_b, running_mean, running_var, users, items, C, n,
+//                                 act) -> scores                            daisy_nfm_scores (eval mode)  NFMRecommender.py:110-209
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -199,6 +201,57 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     return {dE, dX, dW1, db1, dW2, db2};
 }
 
+// NFM.forward in eval mode (running statistics, no dropout) over n pairs: C > 0: (users[e / C], items[e]); items absent:
+// (users[0], e); C == 0: (users[e], items[e]).  W / b: the deep layers' Linear weights and biases; bn_w / bn_b /
+// running_mean / running_var: one entry per stage (FM_layers first) or all empty (batch_norm off).
+at::Tensor nfm_scores(const at::Tensor &P, const at::Tensor &Q, const at::Tensor &ub, const at::Tensor &ib, const at::Tensor &bias,
+                      const at::Tensor &wp, at::TensorList W, at::TensorList b, at::TensorList bn_w, at::TensorList bn_b,
+                      at::TensorList rmean, at::TensorList rvar, const at::Tensor &users, const c10::optional<at::Tensor> &items,
+                      int64_t C, int64_t n, int64_t act) {
+    for (auto *t : {&P, &Q, &ub, &ib, &bias, &wp}) need(*t, at::kFloat, "nfm_scores");
+    need(users, at::kLong, "users");
+    TORCH_CHECK(P.dim() == 2 && Q.dim() == 2 && P.size(1) == Q.size(1), "nfm_scores: shapes of P, Q");
+    const int64_t d = P.size(1), L = (int64_t)W.size();
+    TORCH_CHECK(L <= DAISY_NFM_MAX_LAYERS && b.size() == W.size(), "nfm_scores: W / b: at most ", DAISY_NFM_MAX_LAYERS, " layers");
+    const bool bn = bn_w.size() > 0;
+    TORCH_CHECK(!bn || ((int64_t)bn_w.size() == L + 1 && bn_b.size() == bn_w.size() && rmean.size() == bn_w.size() &&
+                        rvar.size() == bn_w.size()),
+                "nfm_scores: BatchNorm lists need one entry per stage (num_layers + 1)");
+    same_device(P, {&Q, &ub, &ib, &bias, &wp, &users}, "nfm_scores");
+    const c10::OptionalDeviceGuard guard(P.device());
+    daisy_nfm_params p{};
+    p.P = P.data_ptr<float>(); p.Q = Q.data_ptr<float>(); p.ub = ub.data_ptr<float>(); p.ib = ib.data_ptr<float>();
+    p.bias = bias.data_ptr<float>(); p.wp = wp.data_ptr<float>();
+    for (int64_t l = 0; l < L; ++l) {
+        need(W[l], at::kFloat, "W"); need(b[l], at::kFloat, "b");
+        TORCH_CHECK(W[l].numel() == d * d && b[l].numel() == d, "nfm_scores: layer shapes");
+        p.W[l] = W[l].data_ptr<float>(); p.b[l] = b[l].data_ptr<float>();
+    }
+    daisy_nfm_bn_state st{};
+    for (size_t k = 0; bn && k < bn_w.size(); ++k) {
+        for (const at::Tensor *t : {&bn_w[k], &bn_b[k], &rmean[k], &rvar[k]}) {
+            need(*t, at::kFloat, "BatchNorm");
+            TORCH_CHECK(t->numel() == d, "nfm_scores: BatchNorm shapes");
+        }
+        p.bn_w[k] = bn_w[k].data_ptr<float>(); p.bn_b[k] = bn_b[k].data_ptr<float>();
+        st.mean[k] = rmean[k].data_ptr<float>(); st.var[k] = rvar[k].data_ptr<float>();
+    }
+    const int64_t *ip = nullptr;
+    if (items.has_value() && items->defined()) {
+        need(*items, at::kLong, "items");
+        n = items->numel();
+        ip = items->data_ptr<int64_t>();
+    }
+    daisy_nfm_ctx *ctx = nullptr;
+    ok(daisy_nfm_ctx_create(&ctx, 1, (int32_t)d, (int32_t)L, (int32_t)act, bn ? 1 : 0, P.size(0), Q.size(0)));
+    at::Tensor out = at::empty({n}, P.options());
+    const int rc = daisy_nfm_scores(ctx, &p, bn ? &st : nullptr, users.data_ptr<int64_t>(), ip, n, C, 0, 0.f, 0,
+                                    out.data_ptr<float>(), stream_of(P));
+    daisy_nfm_ctx_destroy(ctx);
+    ok(rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(daisyrec, m) {
@@ -212,6 +265,9 @@ TORCH_LIBRARY(daisyrec, m) {
           "int layer) -> (Tensor, Tensor)");
     m.def("ngcf_layer_bwd(Tensor dY, Tensor Y, Tensor norm, Tensor E, Tensor X, Tensor W1, Tensor W2, float mess_p, "
           "int seed, int layer) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("nfm_scores(Tensor P, Tensor Q, Tensor ub, Tensor ib, Tensor bias, Tensor wp, Tensor[] W, Tensor[] b, "
+          "Tensor[] bn_w, Tensor[] bn_b, Tensor[] running_mean, Tensor[] running_var, Tensor users, Tensor? items, int C, "
+          "int n, int act) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP key of a ROCm build
@@ -222,4 +278,5 @@ TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP
     m.impl("bpr_mf_step", &bpr_mf_step);
     m.impl("ngcf_layer_fwd", &ngcf_layer_fwd);
     m.impl("ngcf_layer_bwd", &ngcf_layer_bwd);
+    m.impl("nfm_scores", &nfm_scores);
 }

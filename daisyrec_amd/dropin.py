@@ -42,6 +42,9 @@ def install(sampler=False, front_end=False):
         ref_ng.NGCF = NGCF
     except ImportError:
         pass
+    from .model.NFMRecommender import NFM
+    ref_nf = importlib.import_module("daisy.model.NFMRecommender")
+    ref_nf.NFM = NFM
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -1148,3 +1148,107 @@ def ngcf_wgrad_reduce(ws, n, d_in, d_out, dW1, db1, dW2, db2):
     check(lib.daisy_ngcf_wgrad_reduce(C.c_void_p(ws.data_ptr()), int(n), int(d_in), int(d_out),
                                       _ptr(dW1, torch.float32, "dW1"), _ptr(db1, torch.float32, "db1"),
                                       _ptr(dW2, torch.float32, "dW2"), _ptr(db2, torch.float32, "db2"), _stream()))
+
+
+# ---- NFM (csrc/nfm.hip; NFMRecommender.py:15-209) ---------------------------------------------------------------------
+def _nfm_table(t, num_layers, batch_norm):
+    """daisy_nfm_params from a dict: P, Q, ub, ib, bias, W1.., b1.., wp and (batch_norm) bn_w0.., bn_b0.."""
+    f = torch.float32
+    p = N.NfmParams()
+    for k in ("P", "Q", "ub", "ib", "bias", "wp"):
+        setattr(p, k, _ptr(t[k], f, k))
+    for l in range(1, num_layers + 1):
+        p.W[l - 1] = _ptr(t[f"W{l}"], f, f"W{l}")
+        p.b[l - 1] = _ptr(t[f"b{l}"], f, f"b{l}")
+    if batch_norm:
+        for s in range(num_layers + 1):
+            p.bn_w[s] = _ptr(t[f"bn_w{s}"], f, f"bn_w{s}")
+            p.bn_b[s] = _ptr(t[f"bn_b{s}"], f, f"bn_b{s}")
+    return p
+
+
+def _nfm_bn(bn, num_layers):
+    """daisy_nfm_bn_state from a list of (running_mean, running_var, num_batches_tracked) per stage (None: no BN)."""
+    st = N.NfmBnState()
+    if bn is None:
+        return st
+    for s in range(num_layers + 1):
+        m, v, n = bn[s]
+        st.mean[s] = _ptr(m, torch.float32, f"running_mean{s}")
+        st.var[s] = _ptr(v, torch.float32, f"running_var{s}")
+        st.nbt[s] = _ptr(n, torch.int64, f"num_batches_tracked{s}")
+    return st
+
+
+class NfmContext:
+    """Activation workspace + entry points of the NFM path (daisy_nfm_*)."""
+
+    def __init__(self, max_rows, factors, num_layers, act, batch_norm, user_num, item_num, device=None):
+        self.device = torch.device(device if device is not None else "cuda")
+        self.L, self.d, self.bn = int(num_layers), int(factors), bool(batch_norm)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.daisy_nfm_ctx_create(C.byref(self._h), int(max_rows), int(factors), int(num_layers),
+                                           N.NFM_ACT.get(act, 0) if isinstance(act, str) else int(act), int(bool(batch_norm)),
+                                           int(user_num), int(item_num)))
+        self.max_rows = int(max_rows)
+        self.stats = torch.zeros(N.NFM_STATS_LEN, dtype=torch.float64, device=self.device)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib.daisy_nfm_ctx_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @property
+    def nbytes(self):
+        return int(lib.daisy_nfm_ctx_bytes(self._h))
+
+    def set_path(self, path):
+        """'auto' (the layered step), 'small' (the one-workgroup step, B <= NFM_SMALL_MAX_B) or 'layered': same bits."""
+        check(lib.daisy_nfm_ctx_set_path(self._h, N.NFM_PATHS[path]))
+
+    def scores(self, params, bn, users, items=None, C_=0, n=None, train=False, dropout=0.0, seed=0):
+        """NFM.forward over n pairs (daisy_nfm_scores' three pair layouts); train: training-mode BatchNorm / dropout."""
+        users = users.to(torch.int64).contiguous()
+        if items is not None:
+            items = items.to(torch.int64).contiguous()
+            n = items.numel()
+        out = torch.empty(int(n), dtype=torch.float32, device=self.device)
+        pt, bt = _nfm_table(params, self.L, self.bn), _nfm_bn(bn, self.L)
+        check(lib.daisy_nfm_scores(self._h, C.byref(pt), C.byref(bt), _ptr(users, torch.int64, "users"),
+                                   _ptr(items, torch.int64, "items"), int(n), int(C_), int(bool(train)), float(dropout),
+                                   int(seed) & (2 ** 64 - 1), _ptr(out, torch.float32, "out"), _stream()))
+        return out
+
+    def step_grads(self, params, grads, bn, u, i, j, loss_type=N.LOSS_BPR, reg_1=0.0, reg_2=0.0, dropout=0.0, seed=0,
+                   gamma=1e-10):
+        """NFM.calc_loss + backward for one batch: accumulates into `grads`, updates `bn`; loss in stats[NFST_LOSS]."""
+        pt, gt, bt = _nfm_table(params, self.L, self.bn), _nfm_table(grads, self.L, self.bn), _nfm_bn(bn, self.L)
+        check(lib.daisy_nfm_step_grads(self._h, C.byref(pt), C.byref(gt), C.byref(bt), _ptr(u, torch.int32, "u"),
+                                       _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), u.numel(), int(loss_type),
+                                       float(gamma), float(reg_1), float(reg_2), float(dropout), int(seed) & (2 ** 64 - 1),
+                                       _ptr(self.stats, torch.float64, "stats"), _stream()))
+
+    def fit_epoch(self, params, grads, bn, u, i, j, batch, optim, W, g, loss_type=N.LOSS_BPR, reg_1=0.0, reg_2=0.0,
+                  dropout=0.0, seed_hi=0, step0=0, gamma=1e-10):
+        """One epoch of AbstractRecommender.fit's loop issued by the library (daisy_nfm_fit_epoch): step_grads + the
+        dense optimiser per batch.  step0: the steps taken before (the dropout key of step k is seed_hi | (step0 + k));
+        Adam's bias correction counts optim.t.  Advances optim.t by the number of steps and returns it; the epoch's
+        loss accumulates in stats[NFST_LOSS_SUM]."""
+        n = int(u.numel())
+        steps = (n + int(batch) - 1) // int(batch)
+        W, g = W.view(-1), g.view(-1)
+        st = optim.state_for(W)
+        pt, gt, bt = _nfm_table(params, self.L, self.bn), _nfm_table(grads, self.L, self.bn), _nfm_bn(bn, self.L)
+        f = torch.float32
+        check(lib.daisy_nfm_fit_epoch(self._h, C.byref(pt), C.byref(gt), C.byref(bt), _ptr(u, torch.int32, "u"),
+                                      _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), n, int(batch), int(loss_type),
+                                      float(gamma), float(reg_1), float(reg_2), float(dropout), int(seed_hi) & (2 ** 64 - 1),
+                                      int(step0), int(optim.t), DenseOptimizer.KINDS.index(optim.kind), float(optim.lr), _ptr(W, f, "W"),
+                                      _ptr(g, f, "g"), _ptr(st[0], f, "state0") if len(st) > 0 else None,
+                                      _ptr(st[1], f, "state1") if len(st) > 1 else None, W.numel(),
+                                      _ptr(self.stats, torch.float64, "stats"), _stream()))
+        optim.t += steps
+        return steps

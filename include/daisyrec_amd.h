@@ -720,6 +720,86 @@ int daisy_axpby_f32(float *x, float a, float b, float *y, int64_t n, int32_t zer
 int daisy_csr_row_sum(const int64_t *indptr, const int32_t *cols, const float *X, int64_t rows, int32_t d,
                       float *out, daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * NFM (daisy/model/NFMRecommender.py:15-209).  Stage 0 is the bi-interaction x0 = P[u] * Q[i] followed by
+ * FM_layers (BatchNorm1d when batch_norm, Dropout); stage l = 1..L is Linear(d, d), BatchNorm1d, activation,
+ * Dropout (deep_layers); pred = (h_L + ub[u] + ib[i] + bias) . wp.  factors 1..DAISY_NFM_MAX_FACTORS,
+ * num_layers 0..DAISY_NFM_MAX_LAYERS, fp32.  A pairwise training step forwards two calls of B rows each (positives,
+ * then negatives): each call takes its own batch statistics and updates the running statistics once
+ * (momentum 0.1, eps 1e-5, unbiased running variance), as the reference's two forward() calls do.
+ * Dropout keep bits: drop_keep(seed, DAISY_NFM_DROP_STREAM + stage, row * d + column), rows of the negatives'
+ * call numbered B..2B-1 (daisy_dropout_mask reproduces a stream).  Every reduction runs in a fixed order, no
+ * float atomics: a step is bitwise repeatable.
+ * ---------------------------------------------------------------------- */
+#define DAISY_NFM_MAX_LAYERS 8
+#define DAISY_NFM_MAX_FACTORS 256
+#define DAISY_NFM_DROP_STREAM 0x300u
+#define DAISY_NFM_SMALL_MAX_B 256
+/* the two implementations of a training step (same arithmetic, same bits): the small step runs the whole step in ONE
+ * workgroup (one launch; B <= DAISY_NFM_SMALL_MAX_B), the layered step one launch per phase over all workgroups */
+enum { DAISY_NFM_PATH_AUTO = 0, DAISY_NFM_PATH_SMALL = 1, DAISY_NFM_PATH_LAYERED = 2 };
+typedef enum { DAISY_NFM_ACT_NONE = 0, DAISY_NFM_ACT_RELU = 1, DAISY_NFM_ACT_SIGMOID = 2, DAISY_NFM_ACT_TANH = 3 } daisy_nfm_act;
+typedef struct {
+    float *P, *Q;                                  /* embed_user / embed_item weight [U][d], [I][d] */
+    float *ub, *ib, *bias;                         /* u_bias [U], i_bias [I], bias_ [1] */
+    float *bn_w[DAISY_NFM_MAX_LAYERS + 1];         /* BatchNorm weight / bias of stage s [d] (batch_norm only) */
+    float *bn_b[DAISY_NFM_MAX_LAYERS + 1];
+    float *W[DAISY_NFM_MAX_LAYERS];                /* Linear l+1 weight [d][d], bias [d] */
+    float *b[DAISY_NFM_MAX_LAYERS];
+    float *wp;                                     /* prediction.weight [d] */
+} daisy_nfm_params;
+typedef struct {                                   /* BatchNorm buffers of stage s (batch_norm only) */
+    float *mean[DAISY_NFM_MAX_LAYERS + 1];         /* running_mean [d] */
+    float *var[DAISY_NFM_MAX_LAYERS + 1];          /* running_var [d] */
+    int64_t *nbt[DAISY_NFM_MAX_LAYERS + 1];        /* num_batches_tracked [1] */
+} daisy_nfm_bn_state;
+/* stats vector of a training step (device, double[DAISY_NFM_STATS_LEN]) */
+enum {
+    DAISY_NFM_ST_LOSS = 0,        /* the step's loss (criterion + regulariser) */
+    DAISY_NFM_ST_LOSS_SUM = 1,    /* += loss every step (the epoch's loss) */
+    DAISY_NFM_ST_LOSS_DATA = 2,   /* the criterion */
+    DAISY_NFM_ST_NORM_U = 3,      /* Frobenius norms of the gathered user, positive item, negative item rows */
+    DAISY_NFM_ST_NORM_I = 4,
+    DAISY_NFM_ST_NORM_J = 5,
+    DAISY_NFM_ST_NONFINITE = 6,   /* += 1 for every step whose loss is not finite */
+    DAISY_NFM_STATS_LEN = 8
+};
+typedef struct daisy_nfm_ctx daisy_nfm_ctx;
+/* max_rows: rows of one forward call (the batch size B; daisy_nfm_scores in training mode: the pairs scored).
+ * act: daisy_nfm_act; batch_norm: 0 / 1; user_num, item_num < 2^31. */
+int daisy_nfm_ctx_create(daisy_nfm_ctx **out, int64_t max_rows, int32_t factors, int32_t num_layers, int32_t act,
+                         int32_t batch_norm, int64_t user_num, int64_t item_num);
+int daisy_nfm_ctx_destroy(daisy_nfm_ctx *ctx);
+size_t daisy_nfm_ctx_bytes(const daisy_nfm_ctx *ctx);
+/* which path daisy_nfm_step_grads takes: DAISY_NFM_PATH_AUTO (default: the layered path, the faster of the two at every
+ * measured batch), or forced (a forced small path refuses batches above DAISY_NFM_SMALL_MAX_B) */
+int daisy_nfm_ctx_set_path(daisy_nfm_ctx *ctx, int32_t path);
+/* NFM.calc_loss + backward (:125-151) for one batch (u, i, j)[B] (point-wise losses: j holds the labels): the
+ * gradients accumulate (+=) into `grads` (same layout as params), the running statistics of `bn` are updated, the
+ * loss goes to stats.  reg_1 / reg_2: L1 / Frobenius norms of the gathered embedding rows.  dropout_p in [0, 1).
+ * B must be > 1 when batch_norm (torch's "Expected more than 1 value per channel when training"). */
+int daisy_nfm_step_grads(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_params *grads,
+                         const daisy_nfm_bn_state *bn, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B,
+                         int32_t loss_type, float gamma, float reg_1, float reg_2, float dropout_p, uint64_t seed,
+                         double *stats, daisy_stream_t stream);
+/* one epoch of AbstractRecommender.fit's loop over the batches of (u, i, j)[n]: step k (1-based, counted on from
+ * step0) = daisy_nfm_step_grads with seed = seed_hi | (step0 + k), then the dense optimiser (0 SGD, 1 Adam,
+ * 2 Adagrad, 3 RMSprop; torch defaults) over the flat parameter vector W / gradient g [n_flat] (g cleared).  Adam's
+ * bias correction counts its own steps from opt_step0 (the steps the optimiser has taken: a fresh torch optimiser per
+ * fit starts at 0). */
+int daisy_nfm_fit_epoch(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_params *grads,
+                        const daisy_nfm_bn_state *bn, const int32_t *u, const int32_t *i, const int32_t *j, int64_t n,
+                        int64_t batch, int32_t loss_type, float gamma, float reg_1, float reg_2, float dropout_p,
+                        uint64_t seed_hi, int64_t step0, int64_t opt_step0, int32_t optimizer, float lr, float *W, float *g,
+                        float *state0, float *state1, int64_t n_flat, double *stats, daisy_stream_t stream);
+/* NFM.forward's score of n pairs into out[n]: C > 0: pair e = (users[e / C], items[e]) (rank); items == NULL:
+ * (users[0], e) (full_rank); C == 0 with items: (users[e], items[e]).  train == 0: eval mode (running statistics,
+ * no dropout, one fused kernel).  train != 0: training mode - batch statistics over all n pairs, one update of
+ * the running statistics, dropout_p with `seed` (n <= max_rows). */
+int daisy_nfm_scores(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_bn_state *bn, const int64_t *users,
+                     const int64_t *items, int64_t n, int64_t C, int32_t train, float dropout_p, uint64_t seed, float *out,
+                     daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
