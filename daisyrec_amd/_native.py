@@ -71,6 +71,10 @@ class NfmBnState(C.Structure):
 _np = C.POINTER(NfmParams)
 _nb = C.POINTER(NfmBnState)
 
+VAE_MAX_HIDDEN, VAE_KEEP_STREAM, VAE_EPS_STREAM = 8, 0x400, 0x401
+VST_LOSS, VST_LOSS_SUM, VST_CE, VST_KL, VST_NONFINITE, VST_BAD_ROWS = range(6)
+VAE_STATS_LEN = 8
+
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
     "daisy_last_error": (C.c_char_p, []),
@@ -182,6 +186,15 @@ SIGNATURES = {
     "daisy_nfm_fit_epoch": (C.c_int, [_p, _np, _np, _nb, _p, _p, _p, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _u64,
                                       _i64, _i64, _i32, _f32, _p, _p, _p, _p, _i64, _p, _p]),
     "daisy_nfm_scores": (C.c_int, [_p, _np, _nb, _p, _p, _i64, _i64, _i32, _f32, _u64, _p, _p]),
+    "daisy_vae_ctx_create": (C.c_int, [C.POINTER(_p), _i64, _i64, _i64, _i32, _p, _i32]),
+    "daisy_vae_ctx_destroy": (C.c_int, [_p]),
+    "daisy_vae_ctx_bytes": (_sz, [_p]),
+    "daisy_vae_param_count": (_i64, [_p]),
+    "daisy_vae_step_grads": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _p, _i32, _f32, _f32, _u64, _p,
+                                       _p]),
+    "daisy_vae_fit_epoch": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _f32, C.c_double, _i64, _i64, _u64,
+                                      _i64, _i64, _i32, _f32, _p, _p, _p, _p]),
+    "daisy_vae_scores": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _f32, _u64, _p, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

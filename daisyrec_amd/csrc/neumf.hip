@@ -688,6 +688,21 @@ static void launch_gemm(GemmOp op, hipStream_t s) {
     }
 }
 
+// the fp32 product of neumf_internal.h (csrc/vae.hip's layers): k_gemm with plain stores, or its split-k slices stored apart
+void gemm_f32(const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbn, int64_t sbk, float *C, int64_t ldc,
+              int64_t M, int N, int64_t K, int64_t k_chunk, int64_t slice_stride, hipStream_t s) {
+    GemmOp op{};
+    op.A = A; op.sam = sam; op.sak = sak;
+    op.B = B; op.sbn = sbn; op.sbk = sbk;
+    op.C = C; op.ldc = ldc; op.M = M; op.N = N; op.K = K; op.k_chunk = k_chunk;
+    if (k_chunk < K) {
+        op.slice_stride = slice_stride;
+        launch_gemm<EPI_ATOMIC>(op, s);
+    } else {
+        launch_gemm<EPI_STORE>(op, s);
+    }
+}
+
 
 // two products of the same (N, tile width) in one launch (k_gemm_pair): guarded-loader kernels, fp32
 template <int EPI>

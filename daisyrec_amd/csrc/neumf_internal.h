@@ -51,12 +51,16 @@ __device__ __forceinline__ bf16x8 lds_frag_tr2(const uint16_t *p_lo, const uint1
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// the library's counter hash: 32 random bits of element `idx` of stream `stream` under `seed`
+__host__ __device__ __forceinline__ uint32_t counter_hash(uint64_t seed, uint32_t stream, uint64_t idx) {
+    const uint32_t h = mix32((uint32_t)idx ^ (uint32_t)seed);
+    return mix32(h + (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32) + stream * 0x85EBCA6Bu);
+}
+
 // keep mask of element `idx` of dropout stream `stream` (one stream per MLP layer input)
 __host__ __device__ __forceinline__ bool drop_keep(uint64_t seed, uint32_t stream, uint64_t idx,
                                                    uint32_t thresh) {
-    uint32_t h = mix32((uint32_t)idx ^ (uint32_t)seed);
-    h = mix32(h + (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32) + stream * 0x85EBCA6Bu);
-    return h >= thresh;
+    return counter_hash(seed, stream, idx) >= thresh;
 }
 
 // the threshold of drop_keep for dropout probability p (0: dropout off - every element kept)
@@ -109,6 +113,13 @@ size_t neumf_tower_ws_bytes(int d, int nblocks);
 // one launch of the tower over R rows + the fixed-order reduction of the workgroups' sums into the gradients (+=) and stats
 int neumf_tower_step(const TowerArgs &args, int d, int64_t R, float *gW2, float *gW3, float *gb2, float *gb3, float *gWp,
                      float *gbp, double *stats, float reg_1, float reg_2, hipStream_t s);
+
+// ---- the fp32 MFMA product of csrc/neumf.hip (k_gemm), for csrc/vae.hip: C(m,n) = sum_k A(m,k) B(n,k) with
+// A(m,k) = A[m*sam + k*sak], B(n,k) = B[n*sbn + k*sbk], C(m,n) = C[m*ldc + n].  k_chunk >= K: C is written;
+// k_chunk < K: slice z of the k range [z*k_chunk, (z+1)*k_chunk) STORES its partial product at C + z*slice_stride
+// (slice_stride != 0; the caller sums the slices in a fixed order).
+void gemm_f32(const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbn, int64_t sbk, float *C, int64_t ldc,
+              int64_t M, int N, int64_t K, int64_t k_chunk, int64_t slice_stride, hipStream_t s);
 
 // ---- the small-step kernel (csrc/neumf_mid.hip): a step of at most 1024 rows whose MLP weights fit the LDS - the gather, every
 // layer, the predict layer, the criterion and their backward pass, everything before the scatter, in ONE launch (fp32)

@@ -22,6 +22,8 @@
 //                                                                           (dE without A_hat^T dX: the caller's sparse product)
 //   torch.ops.daisyrec.nfm_scores(P, Q, ub, ib, bias, wp, W, b, bn_w, bn_b, running_mean, running_var, users, items, C, n,
 //                                 act) -> scores                            daisy_nfm_scores (eval mode)  NFMRecommender.py:110-209
+//   torch.ops.daisyrec.vae_scores(W, row_ptr, col, val, users, items, hidden, latent_dim, item_num) -> scores
+//                                                                           daisy_vae_scores (eval mode)  VAECFRecommender.py:79-145
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -30,6 +32,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <vector>
 
 #include "../../include/daisyrec_amd.h"
 
@@ -252,6 +255,48 @@ at::Tensor nfm_scores(const at::Tensor &P, const at::Tensor &Q, const at::Tensor
     return out;
 }
 
+// VAECF.forward in eval mode over the users' history rows (CSR: row_ptr int64, col int32, val float32; W: the flat
+// parameter buffer, encoder.0.weight item-major): [B][C] for candidates items [B][C], or [B][item_num] without them.
+at::Tensor vae_scores(const at::Tensor &W, const at::Tensor &row_ptr, const at::Tensor &col, const at::Tensor &val,
+                      const at::Tensor &users, const c10::optional<at::Tensor> &items, at::IntArrayRef hidden,
+                      int64_t latent_dim, int64_t item_num) {
+    need(W, at::kFloat, "W"); need(row_ptr, at::kLong, "row_ptr"); need(col, at::kInt, "col"); need(val, at::kFloat, "val");
+    need(users, at::kLong, "users");
+    TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.numel() >= 2 && col.numel() == val.numel(), "vae_scores: CSR shapes");
+    TORCH_CHECK((int64_t)hidden.size() <= DAISY_VAE_MAX_HIDDEN, "vae_scores: at most ", DAISY_VAE_MAX_HIDDEN, " hidden layers");
+    same_device(W, {&row_ptr, &col, &val, &users}, "vae_scores");
+    const c10::OptionalDeviceGuard guard(W.device());
+    const int64_t U = row_ptr.numel() - 1, B = users.numel();
+    TORCH_CHECK(B >= 1, "vae_scores: no users");
+    TORCH_CHECK(users.min().item<int64_t>() >= 0 && users.max().item<int64_t>() < U, "vae_scores: user id out of range");
+    const int64_t entries = (row_ptr.index_select(0, users + 1) - row_ptr.index_select(0, users)).sum().item<int64_t>();
+    std::vector<int32_t> hid(hidden.begin(), hidden.end());
+    int64_t C = 0;
+    const int64_t *ip = nullptr;
+    if (items.has_value() && items->defined()) {
+        need(*items, at::kLong, "items");
+        TORCH_CHECK(items->dim() == 2 && items->size(0) == B, "vae_scores: items must be [B, C]");
+        TORCH_CHECK(items->numel() == 0 || (items->min().item<int64_t>() >= 0 && items->max().item<int64_t>() < item_num),
+                    "vae_scores: item id out of range");
+        C = items->size(1);
+        ip = items->data_ptr<int64_t>();
+    }
+    daisy_vae_ctx *ctx = nullptr;
+    ok(daisy_vae_ctx_create(&ctx, B, entries > 0 ? entries : 1, item_num, (int32_t)hid.size(), hid.data(), (int32_t)latent_dim));
+    const int64_t need_params = daisy_vae_param_count(ctx);
+    if (need_params != W.numel()) {
+        daisy_vae_ctx_destroy(ctx);
+        TORCH_CHECK(false, "vae_scores: W holds ", W.numel(), " floats, the layer widths need ", need_params);
+    }
+    at::Tensor out = at::empty({B, ip ? C : item_num}, W.options());
+    const int rc = daisy_vae_scores(ctx, W.data_ptr<float>(), row_ptr.data_ptr<int64_t>(), col.data_ptr<int32_t>(),
+                                    val.data_ptr<float>(), U, users.data_ptr<int64_t>(), B, entries, ip, C, nullptr, nullptr, 0,
+                                    0.f, 0, out.data_ptr<float>(), stream_of(W));
+    daisy_vae_ctx_destroy(ctx);
+    ok(rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(daisyrec, m) {
@@ -268,6 +313,8 @@ TORCH_LIBRARY(daisyrec, m) {
     m.def("nfm_scores(Tensor P, Tensor Q, Tensor ub, Tensor ib, Tensor bias, Tensor wp, Tensor[] W, Tensor[] b, "
           "Tensor[] bn_w, Tensor[] bn_b, Tensor[] running_mean, Tensor[] running_var, Tensor users, Tensor? items, int C, "
           "int n, int act) -> Tensor");
+    m.def("vae_scores(Tensor W, Tensor row_ptr, Tensor col, Tensor val, Tensor users, Tensor? items, int[] hidden, "
+          "int latent_dim, int item_num) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP key of a ROCm build
@@ -279,4 +326,5 @@ TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP
     m.impl("ngcf_layer_fwd", &ngcf_layer_fwd);
     m.impl("ngcf_layer_bwd", &ngcf_layer_bwd);
     m.impl("nfm_scores", &nfm_scores);
+    m.impl("vae_scores", &vae_scores);
 }

@@ -45,6 +45,9 @@ def install(sampler=False, front_end=False):
     from .model.NFMRecommender import NFM
     ref_nf = importlib.import_module("daisy.model.NFMRecommender")
     ref_nf.NFM = NFM
+    from .model.VAECFRecommender import VAECF
+    ref_vae = importlib.import_module("daisy.model.VAECFRecommender")
+    ref_vae.VAECF = VAECF
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

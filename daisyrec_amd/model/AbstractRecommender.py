@@ -568,3 +568,46 @@ class _AdamState:
         for lz in (self.lazy, self.lazy_staged):
             if lz is not None:
                 lz.flush()
+
+
+class AERecommender(GeneralRecommender):
+    """Reference: AbstractRecommender.py:139-167 (the auto-encoder base: dense rating rows gathered from the padded
+    histories of utils.get_history_matrix)."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.user_num = None
+        self.item_num = None
+        self.history_user_id, self.history_item_id = None, None
+        self.history_user_value, self.history_item_value = None, None
+
+    @staticmethod
+    def _rating_rows(history_id, history_value, rows, width, device):
+        """[len(rows), width] float32 with row r = the padded history of rows[r] written entry after entry, the last write
+        of a column winning (index_put_ without accumulation on the host, AbstractRecommender.py:152-156): the padding
+        (column 0, value 0) after a row shorter than the longest erases that row's column 0."""
+        rows = torch.as_tensor(rows).to(history_id.device).long().reshape(-1)
+        ids, vals = history_id[rows], history_value[rows].to(torch.float32)
+        out = torch.zeros(rows.numel(), width, dtype=torch.float32, device=ids.device)
+        if ids.numel():
+            n, L = ids.shape
+            r = torch.arange(n, device=ids.device).repeat_interleave(L)
+            c, v = ids.reshape(-1), vals.reshape(-1)
+            c = torch.where(c < 0, c + width, c)
+            # the last position of every (row, column) pair is the write that stays
+            key = (r * width + c) * max(L, 1) + torch.arange(L, device=ids.device).repeat(n)
+            order = torch.argsort(key)
+            rc = (r * width + c)[order]
+            last = torch.ones_like(rc, dtype=torch.bool)
+            last[:-1] = rc[1:] != rc[:-1]
+            sel = order[last]
+            out[r[sel], c[sel]] = v[sel]
+        return out.to(device)
+
+    def get_user_rating_matrix(self, user):
+        """AbstractRecommender.py:147-158 -> [B, item_num]"""
+        return self._rating_rows(self.history_item_id, self.history_item_value, user, self.item_num, self.device)
+
+    def get_item_rating_matrix(self, item):
+        """AbstractRecommender.py:160-167 -> [B, user_num]"""
+        return self._rating_rows(self.history_user_id, self.history_user_value, item, self.user_num, self.device)

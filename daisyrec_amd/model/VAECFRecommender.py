@@ -1,0 +1,280 @@
+"""Multi-VAE (VAECF) recommender with the reference's interface, trained by HIP kernels.
+
+Mirror of daisy/model/VAECFRecommender.py (class ``VAECF``, an ``AERecommender``): same config keys, attributes
+(``update``, ``history_item_id``, ``encode_layer_dims``, ...) and methods, and the ``nn`` modules built in the same order,
+so a seed gives the reference's initial parameters and ``state_dict`` keys and shapes.  ``fit`` / ``calc_loss`` /
+``rank`` / ``full_rank`` / ``predict`` run through ``daisy_vae_*`` (include/daisyrec_amd.h, csrc/vae.hip): the sparse
+first encoder layer over the users' history rows, every dense layer, the reparameterisation, the log-softmax
+cross-entropy + annealed KL and the backward pass, then one dense optimiser pass over the flat parameter buffer.
+There is no CPU path.
+
+``encoder.0.weight`` ([hidden0, item_num] in torch) is held item-major behind a transposed view: ``state_dict()``,
+``load_state_dict()`` and ``parameters()`` show the reference's shape.  Dropout and the reparameterisation noise use
+the device's counter hash, not torch's generator: the same distributions, a different stream.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .. import _native as N
+from .AbstractRecommender import AERecommender, _tqdm
+
+
+class VAECF(AERecommender):
+    def __init__(self, config):
+        """Config keys as in VAECFRecommender.py:18-61 (multi-vae.yaml + basic.yaml)."""
+        super().__init__(config)
+        self.epochs = config["epochs"]
+        self.lr = config["lr"]
+        self.dropout = config["dropout"]
+
+        self.layers = config["mlp_hidden_size"] if config["mlp_hidden_size"] is not None else [600]
+        self.lat_dim = config["latent_dim"]
+        self.anneal_cap = config["anneal_cap"]
+        self.total_anneal_steps = config["total_anneal_steps"]
+
+        self.user_num = config["user_num"]
+        self.item_num = config["item_num"]
+
+        self.history_item_id = config["history_item_id"].to(self.device)
+        self.history_item_value = config["history_item_value"].to(self.device)
+        self.update = 0
+
+        self.encode_layer_dims = [self.item_num] + self.layers + [self.lat_dim]
+        self.decode_layer_dims = [int(self.lat_dim / 2)] + self.encode_layer_dims[::-1][1:]
+        if len(self.layers) > N.VAE_MAX_HIDDEN or int(self.lat_dim) < 2:
+            raise ValueError(f"VAECF: mlp_hidden_size={self.layers} (at most {N.VAE_MAX_HIDDEN} layers), "
+                             f"latent_dim={self.lat_dim} (>= 2) unsupported")
+
+        self.encoder = self.mlp_layers(self.encode_layer_dims)
+        self.decoder = self.mlp_layers(self.decode_layer_dims)
+
+        self.optimizer = config["optimizer"] if config["optimizer"] != "default" else "adam"
+        self.initializer = config["init_method"] if config["init_method"] != "default" else "xavier_normal"
+        self.early_stop = config["early_stop"]
+
+        self.apply(self._init_weight)
+        self.topk = config["topk"]
+
+        self._flat = None
+        self._csr_cache = None
+        self._sctx = None
+        self._steps = 0           # optimiser steps taken: the noise key of step k is (seed << 32) | k
+        self._score_calls = 0
+
+    def mlp_layers(self, layer_dims):
+        """VAECFRecommender.py:63-69: Linear layers, Tanh between them."""
+        mods = []
+        for k, (d_in, d_out) in enumerate(zip(layer_dims[:-1], layer_dims[1:])):
+            mods.append(nn.Linear(d_in, d_out))
+            if k != len(layer_dims) - 2:
+                mods.append(nn.Tanh())
+        return nn.Sequential(*mods)
+
+    # -- parameters as the kernels see them: ONE flat device buffer, the module's tensors are views -------------------
+    def _flat_views_live(self):
+        if self._flat is None:
+            return False
+        off, base = 0, self._flat.data_ptr()
+        for p in self.parameters():
+            if not p.is_cuda or p.data_ptr() != base + 4 * off:
+                return False
+            off += p.numel()
+        return True
+
+    def _params(self):
+        """Move the parameters into one contiguous device buffer (once; encoder.0.weight item-major), return it."""
+        self._require_device()
+        if not self._flat_views_live():
+            ps = list(self.named_parameters())
+            flat = torch.empty(sum(p.numel() for _, p in ps), dtype=torch.float32, device=self.device)
+            off = 0
+            for name, p in ps:
+                n = p.numel()
+                if name == "encoder.0.weight":
+                    h, I = p.shape
+                    flat[off:off + n].view(I, h).copy_(p.data.t())
+                    p.data = flat[off:off + n].view(I, h).t()
+                else:
+                    flat[off:off + n].copy_(p.data.reshape(-1))
+                    p.data = flat[off:off + n].view(p.shape)
+                off += n
+            self._flat = flat
+        return self._flat
+
+    def _csr(self):
+        """The user rows of R on the device (ops.vae_history_csr), rebuilt when the history tensors change; also the
+        rows' entry counts on the host (the per-batch entry counts the kernels are given)."""
+        key = (id(self.history_item_id), id(self.history_item_value))
+        if self._csr_cache is None or self._csr_cache[0] != key:
+            hid = self.history_item_id.to(self.device)
+            hval = self.history_item_value.to(self.device)
+            csr = ops.vae_history_csr(hid, hval, self.item_num)
+            lens = (csr[0][1:] - csr[0][:-1]).cpu()
+            self._csr_cache = (key, csr, lens)
+        return self._csr_cache[1], self._csr_cache[2]
+
+    @property
+    def _seed_hi(self):
+        return (int(self.seed) & 0xFFFFFFFF) << 32
+
+    def _check_users(self, users):
+        U = int(self.history_item_id.shape[0])
+        if users.numel() and (int(users.min()) < 0 or int(users.max()) >= U):
+            raise IndexError(f"index {int(users.max()) if int(users.max()) >= U else int(users.min())} is out of bounds "
+                             f"for dimension 0 with size {U}")
+
+    def _check_items(self, items):
+        if items.numel() and (int(items.min()) < 0 or int(items.max()) >= self.item_num):
+            raise IndexError(f"index out of range: item ids must lie in [0, {self.item_num})")
+
+    def _ctx(self, rows, entries):
+        return ops.VaeContext(max(int(rows), 1), max(int(entries), 1), self.item_num, self.layers, self.lat_dim,
+                              device=self.device)
+
+    def _score_ctx(self, rows, entries):
+        ctx = self._sctx
+        if ctx is None or ctx.max_batch < rows or ctx.max_entries < entries:
+            if ctx is not None:
+                ctx.close()
+            ctx = self._sctx = self._ctx(max(rows, 1 if ctx is None else ctx.max_batch),
+                                         max(entries, 1 if ctx is None else ctx.max_entries))
+        return ctx
+
+    def _scores(self, users, items=None, keep=None, eps=None):
+        """VAECF.forward's scores in the module's mode: [B, C] for candidates items [B, C], or [B, item_num]."""
+        W = self._params()
+        csr, lens = self._csr()
+        users = torch.as_tensor(users).reshape(-1).to(torch.int64)
+        self._check_users(users)
+        entries = int(lens[users.cpu()].sum()) if users.numel() else 0
+        ctx = self._score_ctx(users.numel(), entries)
+        train = bool(self.training)
+        self._score_calls += 1
+        return ctx.scores(W, csr, users.to(self.device), entries, items=items, train=train,
+                          dropout=self.dropout if train else 0.0, seed=self._seed_hi | (0x80000000 + self._score_calls),
+                          keep=keep, eps=eps)
+
+    # -- reference surface -------------------------------------------------------------------------------------------
+    def reparameterize(self, mu, logvar):
+        """VAECFRecommender.py:71-77 (torch's generator; the kernels draw eps from the device hash)."""
+        if self.training:
+            std = torch.exp(0.5 * logvar)
+            return torch.randn_like(std).mul(std).add_(mu)
+        return mu
+
+    def forward(self, rating_matrix):
+        """VAECFRecommender.py:79-90 needs the encoder output of a dense rating matrix; the HIP path scores users from
+        their history rows instead (rank / full_rank / predict)."""
+        raise NotImplementedError("VAECF.forward(rating_matrix): the HIP path scores users from their history rows "
+                                  "(rank / full_rank / predict); there is no dense-input path")
+
+    def calc_loss(self, batch):
+        """VAECFRecommender.py:92-110: the batch loss (0-dim float64 device tensor, no autograd graph, no parameter
+        change); counts `update` like the reference.  Training-mode noise uses the key of the next optimiser step."""
+        W = self._params()
+        csr, lens = self._csr()
+        user = torch.as_tensor(batch).reshape(-1).to(torch.int64)
+        self._check_users(user)
+        self.update += 1
+        if self.total_anneal_steps > 0:
+            anneal = min(self.anneal_cap, 1. * self.update / self.total_anneal_steps)
+        else:
+            anneal = self.anneal_cap
+        entries = int(lens[user.cpu()].sum())
+        ctx = self._ctx(user.numel(), entries)
+        try:
+            g = torch.zeros_like(W)
+            ctx.step_grads(W, g, csr, user.to(self.device), entries, train=self.training,
+                           dropout=self.dropout if self.training else 0.0, anneal=anneal,
+                           seed=self._seed_hi | (self._steps + 1))
+            return ctx.stats[N.VST_LOSS].clone()
+        finally:
+            ctx.close()
+
+    def fit(self, train_loader):
+        """AbstractRecommender.py:103-137 for VAECF: the epoch's steps (daisy_vae_step_grads + the dense optimiser) are
+        issued by the library in one call; one host sync per epoch (the NaN check is per epoch)."""
+        self._require_device()
+        opt = self._resolve_optimizer()
+        W = self._params()
+        csr, lens = self._csr()
+        data = getattr(train_loader.dataset, "data", None)
+        if data is None:
+            raise TypeError("fit expects a DataLoader over AEDataset (dataset.data = the training users)")
+        users_all = torch.as_tensor(np.asarray(data)).reshape(-1).to(torch.int64)
+        n, B = users_all.numel(), int(train_loader.batch_size)
+        if train_loader.drop_last:
+            n = (n // B) * B
+        self._check_users(users_all[:n])
+        ulens = lens[users_all]
+        max_entries = int(torch.topk(ulens, min(B, ulens.numel())).values.sum()) if ulens.numel() else 0
+        g = torch.zeros_like(W)
+        optim = ops.DenseOptimizer(opt, self.lr)         # a fresh optimiser per fit, as the reference builds one
+        ctx = self._ctx(min(B, max(n, 1)), max_entries)
+        self.epoch_losses, last_loss = [], 0.0
+        try:
+            epochs = range(1, self.epochs + 1)
+            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
+            for epoch in (bar if bar is not None else epochs):
+                self.train()
+                perm = self._epoch_order(train_loader, users_all.numel())      # (drop_last: its first n positions)
+                order = users_all[:n] if perm is None else users_all[perm[:n]]
+                ctx.stats.zero_()
+                if n > 0:
+                    ol = lens[order]
+                    entries = [int(x.sum()) for x in torch.split(ol, B)]
+                    steps = ctx.fit_epoch(W, g, csr, order.to(self.device), B, entries, optim, self.dropout,
+                                          self.anneal_cap, self.total_anneal_steps, self.update,
+                                          seed_hi=self._seed_hi, step0=self._steps)
+                    self._steps += steps
+                    self.update += steps
+                st = ctx.stats.cpu()
+                current_loss = float(st[N.VST_LOSS_SUM])
+                if float(st[N.VST_NONFINITE]) > 0 or current_loss != current_loss:
+                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
+                self.epoch_losses.append(current_loss)
+                if bar is not None:
+                    bar.set_description(f"[Epoch {epoch:03d}]")
+                    bar.set_postfix(loss=current_loss)
+                self.eval()
+                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
+                    self.logger.info("Satisfy early stop mechanism")
+                    break
+                last_loss = current_loss
+        finally:
+            torch.cuda.synchronize()
+            ctx.close()
+
+    def predict(self, u, i):
+        """VAECFRecommender.py:112-119 -> one float."""
+        items = torch.tensor([[int(i)]], dtype=torch.int64)
+        self._check_items(items)
+        return float(self._scores(torch.tensor([int(u)]), items.to(self.device)).cpu().item())
+
+    def rank(self, test_loader):
+        """VAECFRecommender.py:121-138 -> float32 [n_users, topk] like the reference; only the candidates' rows of the
+        last layer are evaluated."""
+        self._params()
+        out = []
+        for us, cands_ids in test_loader:
+            us = torch.as_tensor(us).reshape(-1)
+            cands_ids = torch.as_tensor(cands_ids).to(torch.int64)
+            if cands_ids.dim() == 1:
+                cands_ids = cands_ids.unsqueeze(0)
+            self._check_items(cands_ids)
+            cands_dev = cands_ids.to(self.device)
+            scores = self._scores(us, cands_dev)
+            out.append(ops.topk_from_scores(scores, cands_dev, self.topk))
+        if not out:
+            return np.zeros((0,), dtype=np.float32)
+        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+
+    def full_rank(self, u):
+        """VAECFRecommender.py:140-145 -> int64 [topk] over all items (training items included)."""
+        scores = self._scores(torch.tensor([int(u)]))
+        return ops.full_topk_from_scores(scores.view(-1), self.topk).cpu().numpy()
+

@@ -1252,3 +1252,127 @@ class NfmContext:
                                       _ptr(self.stats, torch.float64, "stats"), _stream()))
         optim.t += steps
         return steps
+
+
+# ---- Multi-VAE (csrc/vae.hip; VAECFRecommender.py) ---------------------------------------------------------------------
+def vae_history_csr(history_item_id, history_item_value, item_num):
+    """The user rows of R as AERecommender.get_user_rating_matrix builds them (AbstractRecommender.py:147-158), as a
+    CSR: (row_ptr int64 [U + 1], col int32 [nnz], val float32 [nnz]), items ascending within a row.  index_put_ without
+    accumulation keeps the LAST write of an item in a row - the padding (item 0, value 0) that follows every row shorter
+    than the longest erases the row's item 0 - and entries whose value is 0 are dropped (they add nothing to R, its
+    norm or the encoder).  Built once per model with torch ops (off the hot path), on the device of the inputs."""
+    ids = torch.as_tensor(history_item_id).to(torch.int64)
+    vals = torch.as_tensor(history_item_value).to(ids.device, torch.float32)
+    if ids.dim() != 2 or vals.shape != ids.shape:
+        raise ValueError(f"history_item_id / history_item_value: expected two [U, L] tensors, got {tuple(ids.shape)} and "
+                         f"{tuple(vals.shape)}")
+    U, L = ids.shape
+    I = int(item_num)
+    if ids.numel() and (int(ids.min()) < -I or int(ids.max()) >= I):
+        raise IndexError(f"index out of range: history item ids must lie in [0, {I})")
+    ids = torch.where(ids < 0, ids + I, ids)                   # (index_put_ wraps negative indices)
+    dev = ids.device
+    user = torch.arange(U, device=dev, dtype=torch.int64).repeat_interleave(L)
+    pos = torch.arange(L, device=dev, dtype=torch.int64).repeat(U)
+    item, v = ids.reshape(-1), vals.reshape(-1)
+    # (user, item) ascending, the last position of every pair last: it is the write that stays
+    order = torch.argsort((user * I + item) * max(L, 1) + pos)
+    ui = (user * I + item)[order]
+    last = torch.ones_like(ui, dtype=torch.bool)
+    if ui.numel() > 1:
+        last[:-1] = ui[1:] != ui[:-1]
+    keep = order[last]
+    keep = keep[v[keep] != 0]
+    row = user[keep]
+    counts = torch.bincount(row, minlength=U) if row.numel() else torch.zeros(U, dtype=torch.int64, device=dev)
+    row_ptr = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+    row_ptr[1:] = torch.cumsum(counts, 0)
+    return row_ptr, item[keep].to(torch.int32).contiguous(), v[keep].contiguous()
+
+
+class VaeContext:
+    """Workspace + entry points of the Multi-VAE path (daisy_vae_*): layer widths, the batch capacity and the flat
+    parameter layout (encoder.0.weight item-major)."""
+
+    def __init__(self, max_batch, max_entries, item_num, hidden, latent_dim, device=None):
+        self.device = torch.device(device if device is not None else "cuda")
+        self.hidden = [int(h) for h in hidden]
+        hid = (C.c_int32 * max(len(self.hidden), 1))(*self.hidden)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.daisy_vae_ctx_create(C.byref(self._h), int(max_batch), int(max_entries), int(item_num),
+                                           len(self.hidden), hid, int(latent_dim)))
+        self.max_batch, self.max_entries, self.item_num = int(max_batch), int(max_entries), int(item_num)
+        self.stats = torch.zeros(N.VAE_STATS_LEN, dtype=torch.float64, device=self.device)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib.daisy_vae_ctx_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @property
+    def nbytes(self):
+        return int(lib.daisy_vae_ctx_bytes(self._h))
+
+    @property
+    def param_count(self):
+        return int(lib.daisy_vae_param_count(self._h))
+
+    @staticmethod
+    def _csr(csr):
+        row_ptr, col, val = csr
+        return (_ptr(row_ptr, torch.int64, "row_ptr"), _ptr(col, torch.int32, "col"), _ptr(val, torch.float32, "val"),
+                row_ptr.numel() - 1)
+
+    def step_grads(self, W, g, csr, users, n_entries, keep=None, eps=None, train=True, dropout=0.5, anneal=0.0, seed=0):
+        """VAECF.calc_loss + backward for users [B] (int64 device): gradients into g (zero on entry), the loss into
+        stats[VST_LOSS].  keep: uint8 [n_entries] / eps: float32 [B, lat // 2] (None: the device hash)."""
+        rp, cp, vp, U = self._csr(csr)
+        users = users.to(torch.int64).contiguous()
+        check(lib.daisy_vae_step_grads(self._h, _ptr(W, torch.float32, "W"), _ptr(g, torch.float32, "g"), rp, cp, vp, U,
+                                       _ptr(users, torch.int64, "users"), users.numel(), int(n_entries),
+                                       _ptr(keep, torch.uint8, "keep"), _ptr(eps, torch.float32, "eps"), int(bool(train)),
+                                       float(dropout), float(anneal), int(seed) & (2 ** 64 - 1),
+                                       _ptr(self.stats, torch.float64, "stats"), _stream()))
+
+    def fit_epoch(self, W, g, csr, users, batch, entries, optim, dropout, anneal_cap, total_anneal_steps, update0,
+                  seed_hi=0, step0=0):
+        """One epoch of AbstractRecommender.fit's loop issued by the library (daisy_vae_fit_epoch).  users: int64 device
+        [n] in epoch order; entries: the history entries of every batch (host).  Advances optim.t and returns the
+        number of steps; the losses accumulate in stats[VST_LOSS_SUM]."""
+        rp, cp, vp, U = self._csr(csr)
+        n = int(users.numel())
+        steps = (n + int(batch) - 1) // int(batch)
+        ent = (C.c_int64 * steps)(*[int(x) for x in entries])
+        W, g = W.view(-1), g.view(-1)
+        st = optim.state_for(W)
+        f = torch.float32
+        check(lib.daisy_vae_fit_epoch(self._h, _ptr(W, f, "W"), _ptr(g, f, "g"), rp, cp, vp, U,
+                                      _ptr(users, torch.int64, "users"), n, int(batch), ent, float(dropout),
+                                      float(anneal_cap), int(total_anneal_steps), int(update0), int(seed_hi) & (2 ** 64 - 1),
+                                      int(step0), int(optim.t), DenseOptimizer.KINDS.index(optim.kind), float(optim.lr),
+                                      _ptr(st[0], f, "state0") if len(st) > 0 else None,
+                                      _ptr(st[1], f, "state1") if len(st) > 1 else None,
+                                      _ptr(self.stats, torch.float64, "stats"), _stream()))
+        optim.t += steps
+        return steps
+
+    def scores(self, W, csr, users, n_entries, items=None, train=False, dropout=0.0, seed=0, keep=None, eps=None):
+        """VAECF.forward's scores of users [B]: [B, item_num], or [B, C] for candidates items [B, C] (int64)."""
+        rp, cp, vp, U = self._csr(csr)
+        users = users.to(torch.int64).contiguous()
+        B = users.numel()
+        if items is not None:
+            items = items.to(torch.int64).contiguous()
+            Cn = items.shape[1]
+            out = torch.empty(B, Cn, dtype=torch.float32, device=self.device)
+        else:
+            Cn = 0
+            out = torch.empty(B, self.item_num, dtype=torch.float32, device=self.device)
+        check(lib.daisy_vae_scores(self._h, _ptr(W, torch.float32, "W"), rp, cp, vp, U, _ptr(users, torch.int64, "users"), B,
+                                   int(n_entries), _ptr(items, torch.int64, "items"), int(Cn), _ptr(keep, torch.uint8, "keep"),
+                                   _ptr(eps, torch.float32, "eps"), int(bool(train)), float(dropout),
+                                   int(seed) & (2 ** 64 - 1), _ptr(out, torch.float32, "out"), _stream()))
+        return out

@@ -800,6 +800,66 @@ int daisy_nfm_scores(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const d
                      const int64_t *items, int64_t n, int64_t C, int32_t train, float dropout_p, uint64_t seed, float *out,
                      daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Multi-VAE (daisy/model/VAECFRecommender.py, VAECF).  Encoder [I] + hidden + [lat], decoder [lat/2] +
+ * reversed(hidden) + [I], Linear layers with Tanh between them, fp32.  The parameters live in ONE flat buffer W in the
+ * module's order (encoder.0.weight, encoder.0.bias, encoder.2.weight, ..., decoder.*): every tensor as torch lays it
+ * out except encoder.0.weight, which is stored item-major ([I][hidden0], the transpose of torch's [hidden0][I]) so
+ * that the sparse first layer reads whole rows.  The gradient buffer g has the same layout and must be zero on entry
+ * (the dense optimisers leave it so).
+ * The user histories are a CSR over users (row_ptr [user_num + 1], col int32, val float32; entries with value 0
+ * dropped, items ascending within a row).  A batch of B users holds the concatenation of its rows' entries (n_entries
+ * of them, the caller's count).  Noise: keep[n_entries] (one byte per batch entry, 0 = dropped) and eps[B][lat/2]
+ * (the reparameterisation's normal draws) when given; otherwise keep = drop_keep(seed, DAISY_VAE_KEEP_STREAM, entry)
+ * and eps = Box-Muller over the counter hash of (seed, DAISY_VAE_EPS_STREAM, b * (lat/2) + j).  Every reduction runs
+ * in a fixed order, no float atomics: a step is bitwise repeatable.
+ * ---------------------------------------------------------------------- */
+#define DAISY_VAE_MAX_HIDDEN 8
+#define DAISY_VAE_KEEP_STREAM 0x400u
+#define DAISY_VAE_EPS_STREAM 0x401u
+enum {
+    DAISY_VAE_ST_LOSS = 0,        /* the step's loss (CE + anneal * KL) */
+    DAISY_VAE_ST_LOSS_SUM = 1,    /* += loss every step (the epoch's loss) */
+    DAISY_VAE_ST_CE = 2,          /* -(log_softmax(z) * R).sum(1).mean() */
+    DAISY_VAE_ST_KL = 3,          /* -0.5 * mean(sum(1 + logvar - mu^2 - exp(logvar))) (before anneal) */
+    DAISY_VAE_ST_NONFINITE = 4,   /* += 1 for every step whose loss is not finite */
+    DAISY_VAE_ST_BAD_ROWS = 5,    /* += 1 per batch row whose user id is out of range or whose entries overflow n_entries */
+    DAISY_VAE_STATS_LEN = 8
+};
+typedef struct daisy_vae_ctx daisy_vae_ctx;
+/* max_batch: users per step or scoring call; max_entries: history entries of such a batch (at most); hidden[n_hidden]:
+ * mlp_hidden_size (0 .. DAISY_VAE_MAX_HIDDEN layers, widths >= 1); latent_dim >= 2; item_num < 2^24. */
+int daisy_vae_ctx_create(daisy_vae_ctx **out, int64_t max_batch, int64_t max_entries, int64_t item_num, int32_t n_hidden,
+                         const int32_t *hidden, int32_t latent_dim);
+int daisy_vae_ctx_destroy(daisy_vae_ctx *ctx);
+size_t daisy_vae_ctx_bytes(const daisy_vae_ctx *ctx);
+/* floats of the flat parameter buffer (0 for NULL) */
+int64_t daisy_vae_param_count(const daisy_vae_ctx *ctx);
+/* VAECF.calc_loss + backward for the users[B] (int64): gradients into g, loss into stats.  train != 0: dropout_p on
+ * the input and z = mu + eps * exp(logvar / 2); train == 0: eval mode (no dropout, z = mu).  anneal: the KL weight of
+ * this step (min(anneal_cap, update / total_anneal_steps), rounded to fp32). */
+int daisy_vae_step_grads(daisy_vae_ctx *ctx, const float *W, float *g, const int64_t *row_ptr, const int32_t *col,
+                         const float *val, int64_t user_num, const int64_t *users, int64_t B, int64_t n_entries,
+                         const uint8_t *keep, const float *eps, int32_t train, float dropout_p, float anneal, uint64_t seed,
+                         double *stats, daisy_stream_t stream);
+/* one epoch of AbstractRecommender.fit's loop over users[n] in epoch order, batches of `batch`: step k (1-based,
+ * counted on from step0) = daisy_vae_step_grads in training mode with the device noise of seed = seed_hi | (step0 + k)
+ * and anneal = min(anneal_cap, (update0 + k) / total_anneal_steps) (anneal_cap when total_anneal_steps <= 0), then
+ * the dense optimiser (0 SGD, 1 Adam, 2 Adagrad, 3 RMSprop; torch defaults) over W / g (g cleared).  entries[k - 1]
+ * (host memory): n_entries of batch k.  Adam's bias correction counts from opt_step0. */
+int daisy_vae_fit_epoch(daisy_vae_ctx *ctx, float *W, float *g, const int64_t *row_ptr, const int32_t *col, const float *val,
+                        int64_t user_num, const int64_t *users, int64_t n, int64_t batch, const int64_t *entries,
+                        float dropout_p, double anneal_cap, int64_t total_anneal_steps, int64_t update0, uint64_t seed_hi,
+                        int64_t step0, int64_t opt_step0, int32_t optimizer, float lr, float *state0, float *state1,
+                        double *stats, daisy_stream_t stream);
+/* VAECF.forward's scores of the users[B]: items == NULL: out[B][item_num] (every item); otherwise out[B][C] for the
+ * candidates items[B][C] (int64, ids checked by the caller), through the candidates' rows of the last layer only.
+ * train / keep / eps / dropout_p / seed as in daisy_vae_step_grads. */
+int daisy_vae_scores(daisy_vae_ctx *ctx, const float *W, const int64_t *row_ptr, const int32_t *col, const float *val,
+                     int64_t user_num, const int64_t *users, int64_t B, int64_t n_entries, const int64_t *items, int64_t C,
+                     const uint8_t *keep, const float *eps, int32_t train, float dropout_p, uint64_t seed, float *out,
+                     daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
