@@ -10,10 +10,13 @@ device is present.
 from __future__ import annotations
 
 import logging
+import math
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
+from torch.utils.data import RandomSampler, SequentialSampler
 
 from .. import ops
 
@@ -188,8 +191,6 @@ class GeneralRecommender(AbstractRecommender):
         global torch RNG exactly like the reference run (dataset.py:5-7 ->
         torch DataLoader): `_BaseDataLoaderIter.__init__` draws `_base_seed`, then
         RandomSampler draws its own seed and calls torch.randperm(n, generator)."""
-        from torch.utils.data import RandomSampler, SequentialSampler
-
         torch.empty((), dtype=torch.int64).random_(generator=train_loader.generator)  # _base_seed
         sampler = train_loader.sampler
         if isinstance(sampler, SequentialSampler):
@@ -204,6 +205,74 @@ class GeneralRecommender(AbstractRecommender):
             return torch.randperm(n, generator=gen)
         return torch.as_tensor(list(iter(sampler)), dtype=torch.int64)
 
+    @property
+    def _seed_hi(self):
+        """high word of the device hash keys (dropout masks, noise): the low word counts steps / calls"""
+        return (int(self.seed) & 0xFFFFFFFF) << 32
+
+    def _train_rows(self, train_loader, columns=3, expects="BasicDataset (dataset.data = int32 [N,3] triples)"):
+        """(rows, n, B) of a fit: `dataset.data` as int32 [N, 3] device triples (columns=1: the int64 host vector of
+        AEDataset's users), the rows one epoch trains (drop_last cuts the tail) and the loader's batch size."""
+        data = getattr(train_loader.dataset, "data", None)
+        if data is None:
+            raise TypeError(f"fit expects a DataLoader over {expects}")
+        rows = torch.as_tensor(data if isinstance(data, torch.Tensor) else np.asarray(data))
+        if columns == 1:
+            rows = rows.reshape(-1).to(torch.int64)
+        else:
+            rows = rows.to(torch.int32).contiguous().to(self.device)
+        n, B = rows.shape[0], int(train_loader.batch_size)
+        if train_loader.drop_last:
+            n = (n // B) * B
+        return rows, n, B
+
+    def _epoch_rows(self, train_loader, rows, n):
+        """the n rows of one epoch in the DataLoader's order (draws from the torch RNG like one pass over the loader)"""
+        perm = self._epoch_order(train_loader, rows.shape[0])
+        return rows[:n] if perm is None else rows[perm[:n].to(rows.device)]
+
+    def _run_epochs(self, run_epoch, progress=True):
+        """The epoch loop of AbstractRecommender.py:112-137, for every model: `run_epoch(epoch)` trains one epoch and
+        returns (loss sum, non-finite step losses) as host floats - the one host sync of the epoch is its own.  The
+        caller owns the native contexts (try: ... finally: synchronize and close)."""
+        self.epoch_losses = []
+        epochs = range(1, self.epochs + 1)
+        bar = _tqdm(epochs) if (progress and self.show_progress and _tqdm is not None) else None
+        last_loss = 0.0
+        for epoch in (bar if bar is not None else epochs):
+            self.train()
+            current_loss, nonfinite = run_epoch(epoch)
+            if nonfinite > 0 or not math.isfinite(current_loss):
+                # AbstractRecommender.py:122-123 (checked once per epoch instead of per batch)
+                raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
+            self.epoch_losses.append(current_loss)
+            log_path = os.environ.get("DAISY_AMD_EPOCH_LOG")    # evidence trail of driver runs (tests/test_gpu_driver.py)
+            if log_path:
+                with open(log_path, "a") as fh:
+                    fh.write(f"{type(self).__name__} epoch {epoch} loss {current_loss!r}\n")
+            if bar is not None:
+                bar.set_description(f"[Epoch {epoch:03d}]")
+                bar.set_postfix(loss=current_loss)
+            self.eval()
+            if abs(current_loss - last_loss) < 1e-5 and self.early_stop:       # AbstractRecommender.py:132-137
+                self.logger.info("Satisfy early stop mechanism")
+                break
+            last_loss = current_loss
+
+    def _rank_loader(self, test_loader, topk_of):
+        """The loop of every `rank`: topk_of(us [Bu], cands_ids [Bu, C]) -> int64 [Bu, topk] per batch of the loader;
+        float32 [n_users, topk] like the reference (ids are concatenated onto a float tensor there)."""
+        out = []
+        for us, cands_ids in test_loader:
+            us = torch.as_tensor(us).to(self.device).reshape(-1)
+            cands_ids = torch.as_tensor(cands_ids).to(self.device)
+            if cands_ids.dim() == 1:
+                cands_ids = cands_ids.unsqueeze(0)
+            out.append(topk_of(us, cands_ids))
+        if not out:
+            return np.zeros((0,), dtype=np.float32)
+        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+
     def _sharded_world(self):
         """ranks that share this fit: torch.distributed initialised with more than one rank and
         config['shard_users'] not switched off (the reference is single device, AbstractRecommender.py:99)"""
@@ -217,7 +286,6 @@ class GeneralRecommender(AbstractRecommender):
         """epoch position of this rank's rows: the order one pass over the DataLoader would use (replayed from the
         torch RNG exactly like the single-device fit, so every rank draws the same permutation), the keyed device
         shuffle, or the identity"""
-        from torch.utils.data import SequentialSampler
         if self.shuffle_mode == "device" and not isinstance(train_loader.sampler, SequentialSampler):
             return ops.feistel_positions_at(row_ids, n, self.seed, epoch)
         perm = self._epoch_order(train_loader, len(train_loader.dataset))
@@ -239,7 +307,6 @@ class GeneralRecommender(AbstractRecommender):
         up to summation order (UserShardedBprTrainer: two small all-reduces, reduce-scatter of the item
         gradient, all-gather of the updated item rows per step).  At the end every rank holds the whole P."""
         import torch.distributed as dist
-        from torch.utils.data import SequentialSampler
         from ..sharding import UserShardedBprTrainer, user_range
         world, rank = dist.get_world_size(), dist.get_rank()
         P, Q = self._tables()
@@ -286,46 +353,38 @@ class GeneralRecommender(AbstractRecommender):
         self.last_exchange = dict(trainer.wire_bytes, slices=trainer.slices)
         acc = torch.zeros(2, dtype=torch.float64, device=P.device)
         nb = (n + B - 1) // B
-        last_loss = 0.0
+
+        def run_epoch(epoch):
+            if n_loc and dense:
+                # the phase kernels read one sorted batch at a time: the rank's rows in epoch order, cut where the
+                # global batches end
+                pos_loc = self._epoch_positions(train_loader, n, epoch, row_ids)
+                order = torch.argsort(pos_loc)
+                cuts = torch.searchsorted(pos_loc[order].contiguous(),
+                                          torch.arange(nb + 1, device=P.device, dtype=torch.int64) * B).cpu().tolist()
+            elif n_loc:
+                plan.build_positions(index, self._epoch_positions(train_loader, n, epoch, row_ids), n, B)
+            elif not (self.shuffle_mode == "device" and not isinstance(train_loader.sampler, SequentialSampler)):
+                # a rank without rows: the replayed DataLoader pass draws from the torch RNG, which has to stay in
+                # step with the other ranks; the device shuffle draws nothing (and has no rows to place here)
+                self._epoch_order(train_loader, len(train_loader.dataset))
+            acc.zero_()
+            for k in range(nb):
+                if dense and n_loc and cuts[k + 1] > cuts[k]:
+                    stats = trainer.step_from_triples(mine, idx=order[cuts[k]:cuts[k + 1]].contiguous(), validate=(epoch == 1))
+                else:
+                    stats = trainer.step_from_plan(plan, k)        # (plan None / no row of batch k: the rank only joins the exchanges)
+                loss = stats[ops.N.ST_LOSS]
+                acc[0] += loss
+                acc[1] += (~torch.isfinite(loss)).to(torch.float64)
+            host = acc.cpu()
+            return float(host[0]), float(host[1])
+
         try:
             if n_loc and not dense:
                 index = ops.TrainIndex(mine, hi - lo, I, user_base=lo, pointwise=pointwise_rows)
                 plan = ops.EpochPlan(n_loc, hi - lo, I, device=P.device)
-            for epoch in range(1, self.epochs + 1):
-                self.train()
-                if n_loc and dense:
-                    # the phase kernels read one sorted batch at a time: the rank's rows in epoch order, cut where the
-                    # global batches end
-                    pos_loc = self._epoch_positions(train_loader, n, epoch, row_ids)
-                    order = torch.argsort(pos_loc)
-                    cuts = torch.searchsorted(pos_loc[order].contiguous(),
-                                              torch.arange(nb + 1, device=P.device, dtype=torch.int64) * B).cpu().tolist()
-                elif n_loc:
-                    plan.build_positions(index, self._epoch_positions(train_loader, n, epoch, row_ids), n, B)
-                elif not (self.shuffle_mode == "device" and not isinstance(train_loader.sampler, SequentialSampler)):
-                    # a rank without rows: the replayed DataLoader pass draws from the torch RNG, which has to stay in
-                    # step with the other ranks; the device shuffle draws nothing (and has no rows to place here)
-                    self._epoch_order(train_loader, len(train_loader.dataset))
-                acc.zero_()
-                for k in range(nb):
-                    if dense and n_loc and cuts[k + 1] > cuts[k]:
-                        stats = trainer.step_from_triples(mine, idx=order[cuts[k]:cuts[k + 1]].contiguous(), validate=(epoch == 1))
-                    else:
-                        stats = trainer.step_from_plan(plan, k)        # (plan None / no row of batch k: the rank only joins the exchanges)
-                    loss = stats[ops.N.ST_LOSS]
-                    acc[0] += loss
-                    acc[1] += (~torch.isfinite(loss)).to(torch.float64)
-                host = acc.cpu()
-                current_loss = float(host[0])
-                if float(host[1]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                self.eval()
-                delta_loss = float(current_loss - last_loss)
-                if (abs(delta_loss) < 1e-5) and self.early_stop:       # AbstractRecommender.py:132-137
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch, progress=False)      # (no bar per rank)
             if trainer.adam is not None:                               # the rows no batch referenced lately -> the last step
                 trainer.adam.flush(ctx)
             for r in range(world):                                     # every rank ends with the whole user table
@@ -358,14 +417,7 @@ class GeneralRecommender(AbstractRecommender):
         opt = self._resolve_optimizer()
         loss_id = self._build_criterion(self.loss_type)
         item_mode = ops.ITEM_MODES[self.item_mode]
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int32 [N,3] triples)")
-        triples = torch.as_tensor(data).to(torch.int32).contiguous().to(self.device)
-        n = triples.shape[0]
-        B = int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         self.epoch_losses = []
         if n == 0:
             # an empty loader: the reference's batch loop does not run, every epoch's loss is 0.0
@@ -426,68 +478,50 @@ class GeneralRecommender(AbstractRecommender):
         if item_mode == ops.ITEM_MODES["fused"] and not staged and B > ops.SMALL_BATCH_MAX:
             item_mode = ops.ITEM_MODES["chunked"]
         index = None
-        last_loss = 0.0
+        device_shuffle = self.shuffle_mode == "device" and not isinstance(train_loader.sampler, SequentialSampler)
+
+        def run_epoch(epoch):
+            if device_shuffle:
+                order, perm = "feistel", None
+            else:
+                perm = self._epoch_order(train_loader, triples.shape[0])
+                if perm is not None:
+                    if n < triples.shape[0]:            # drop_last: the first n positions of the order
+                        perm = perm[:n]
+                        if bool((perm >= n).any()):
+                            raise NotImplementedError("drop_last with a shuffled loader is not supported on "
+                                                      "the HIP path (the dropped rows change per epoch)")
+                    perm = perm.contiguous().to(self.device)
+                order = "identity" if perm is None else "perm"
+            # the epoch laid out batch by batch, in the DataLoader's order
+            if staged:
+                plan.build_indexed(index, B, order=order, perm=perm, seed=self.seed, epoch=epoch)
+            else:
+                plan.build(triples, B, order=order, perm=perm, seed=self.seed, epoch=epoch, n_triples=n,
+                           user_sorted=user_sorted, pointwise=pointwise)
+            ctx.epoch_acc.zero_()
+            if adam is None:
+                ctx.fit_epoch_sgd(plan, P, Q, self.lr, self.reg_1, self.reg_2, loss_type=loss_id,
+                                  item_mode=item_mode)
+            elif adam.kind == "adam" and biases is None and (
+                    staged or (self.lazy_adam is not False and item_mode in (ops.ITEM_MODES["fused"], ops.ITEM_MODES["chunked"])
+                               and ops.LazyAdam.small_epoch_pays(ctx, plan, loss_id))):
+                # the epoch as ONE enqueue (daisy_bpr_fit_epoch_adam), like the SGD loop: at the reference's batch
+                # sizes a host round trip per batch would bound the fit.  B <= 256 (sorted plan): every step of the
+                # epoch inside one persistent workgroup (csrc/bpr_small.hip, the Adam form)
+                adam.staged_epoch(ctx, plan, self.reg_1, self.reg_2, loss_id)
+            else:
+                for k in range(plan.num_batches):
+                    ctx.set_batch_from_plan(plan, k)
+                    adam.step(ctx, P, Q, self.reg_1, self.reg_2, loss_id, item_mode)
+                adam.flush()
+            acc = ctx.epoch_acc.cpu()
+            return float(acc[0]), float(acc[1])
+
         try:
             if staged:      # indexed once per fit (also validates the id ranges)
                 index = ops.TrainIndex(triples[:n], P.shape[0], Q.shape[0], user_sorted=user_sorted, pointwise=pointwise)
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                from torch.utils.data import SequentialSampler
-                if self.shuffle_mode == "device" and not isinstance(train_loader.sampler, SequentialSampler):
-                    order, perm = "feistel", None
-                else:
-                    perm = self._epoch_order(train_loader, triples.shape[0])
-                    if perm is not None:
-                        if n < triples.shape[0]:            # drop_last: the first n positions of the order
-                            perm = perm[:n]
-                            if bool((perm >= n).any()):
-                                raise NotImplementedError("drop_last with a shuffled loader is not supported on "
-                                                          "the HIP path (the dropped rows change per epoch)")
-                        perm = perm.contiguous().to(self.device)
-                    order = "identity" if perm is None else "perm"
-                # the epoch laid out batch by batch, in the DataLoader's order
-                if staged:
-                    plan.build_indexed(index, B, order=order, perm=perm, seed=self.seed, epoch=epoch)
-                else:
-                    plan.build(triples, B, order=order, perm=perm, seed=self.seed, epoch=epoch, n_triples=n,
-                               user_sorted=user_sorted, pointwise=pointwise)
-                ctx.epoch_acc.zero_()
-                if adam is None:
-                    ctx.fit_epoch_sgd(plan, P, Q, self.lr, self.reg_1, self.reg_2, loss_type=loss_id,
-                                      item_mode=item_mode)
-                elif adam.kind == "adam" and biases is None and (
-                        staged or (self.lazy_adam is not False and item_mode in (ops.ITEM_MODES["fused"], ops.ITEM_MODES["chunked"])
-                                   and ops.LazyAdam.small_epoch_pays(ctx, plan, loss_id))):
-                    # the epoch as ONE enqueue (daisy_bpr_fit_epoch_adam), like the SGD loop: at the reference's batch
-                    # sizes a host round trip per batch would bound the fit.  B <= 256 (sorted plan): every step of the
-                    # epoch inside one persistent workgroup (csrc/bpr_small.hip, the Adam form)
-                    adam.staged_epoch(ctx, plan, self.reg_1, self.reg_2, loss_id)
-                else:
-                    for k in range(plan.num_batches):
-                        ctx.set_batch_from_plan(plan, k)
-                        adam.step(ctx, P, Q, self.reg_1, self.reg_2, loss_id, item_mode)
-                    adam.flush()
-                acc = ctx.epoch_acc.cpu()
-                current_loss = float(acc[0])
-                if float(acc[1]) > 0 or current_loss != current_loss:
-                    # AbstractRecommender.py:122-123 (checked once per epoch instead of per batch)
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                log_path = os.environ.get("DAISY_AMD_EPOCH_LOG")    # evidence trail of driver runs (tests/test_gpu_driver.py)
-                if log_path:
-                    with open(log_path, "a") as fh:
-                        fh.write(f"{type(self).__name__} epoch {epoch} loss {current_loss!r}\n")
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                delta_loss = float(current_loss - last_loss)
-                if (abs(delta_loss) < 1e-5) and self.early_stop:       # AbstractRecommender.py:132-137
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender, _tqdm
+from .AbstractRecommender import GeneralRecommender
 
 
 class Item2Vec(GeneralRecommender):
@@ -72,46 +72,26 @@ class Item2Vec(GeneralRecommender):
         """AbstractRecommender.py:103-137, then the user-embedding build of Item2VecRecommender.py:53-59."""
         opt = self._resolve_optimizer()
         Uemb, S = self._tables()
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int [N,3] triples)")
-        triples = torch.as_tensor(np.asarray(data)).to(torch.int32).contiguous().to(S.device)
-        n, B = triples.shape[0], int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         gA, gB = torch.zeros_like(S), torch.zeros_like(S)
         optim = ops.DenseOptimizer(opt, self.lr)
         ctx = ops.BprContext(min(B, max(n, 1)), S.shape[1], S.shape[0], S.shape[0], device=S.device)
         ctx.set_pointwise(True)
-        self.epoch_losses, last_loss, step = [], 0.0, 0
+
+        def run_epoch(epoch):
+            order = self._epoch_rows(train_loader, triples, n)
+            ctx.epoch_acc.zero_()
+            for s in range(0, n, B):
+                rows = order[s:s + B]
+                t, c, y = (rows[:, k].contiguous() for k in range(3))
+                self._step(ctx, S, gA, gB, t, c, y)
+                optim.next_step()
+                optim.step(S, gA)          # also clears the gradient
+            acc = ctx.epoch_acc.cpu()
+            return float(acc[0]), float(acc[1])
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                perm = self._epoch_order(train_loader, triples.shape[0])
-                order = triples[:n] if perm is None else triples[perm[:n].to(S.device)]
-                ctx.epoch_acc.zero_()
-                for s in range(0, n, B):
-                    rows = order[s:s + B]
-                    t, c, y = (rows[:, k].contiguous() for k in range(3))
-                    step += 1
-                    self._step(ctx, S, gA, gB, t, c, y)
-                    optim.next_step()
-                    optim.step(S, gA)          # also clears the gradient
-                acc = ctx.epoch_acc.cpu()
-                current_loss = float(acc[0])
-                if float(acc[1]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -131,16 +111,7 @@ class Item2Vec(GeneralRecommender):
     def rank(self, test_loader):
         """:82-101 -> float32 [n_users, topk]"""
         Uemb, S = self._tables()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).to(S.device)
-            cands_ids = torch.as_tensor(cands_ids).to(S.device)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
-            out.append(ops.mf_rank_topk(Uemb, S, us.reshape(-1), cands_ids, self.topk))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+        return self._rank_loader(test_loader, lambda us, cands_ids: ops.mf_rank_topk(Uemb, S, us, cands_ids, self.topk))
 
     def full_rank(self, u):
         """:103-112 -> int64 [topk]"""

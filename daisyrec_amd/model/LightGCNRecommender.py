@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender, _tqdm
+from ._flat import flatten_parameters, views_live
+from .AbstractRecommender import GeneralRecommender
 
 
 class LightGCN(GeneralRecommender):
@@ -69,14 +70,8 @@ class LightGCN(GeneralRecommender):
         """[P; Q] as ONE contiguous device buffer (get_ego_embeddings, :109-115, without the copy):
         the two nn.Embedding weights become views of it."""
         self._require_device()
-        if self._flat is None or not self.embed_user.weight.is_cuda:
-            U, I, d = self.user_num, self.item_num, self.factors
-            flat = torch.empty((U + I) * d, dtype=torch.float32, device=self.device)
-            flat[:U * d].copy_(self.embed_user.weight.data.reshape(-1))
-            flat[U * d:].copy_(self.embed_item.weight.data.reshape(-1))
-            self.embed_user.weight.data = flat[:U * d].view(U, d)
-            self.embed_item.weight.data = flat[U * d:].view(I, d)
-            self._flat = flat
+        if not views_live(self._flat, self.parameters()):
+            self._flat = flatten_parameters(self.named_parameters(), self.device)
         return self._flat.view(self.user_num + self.item_num, self.factors)
 
     def _adj(self):
@@ -156,47 +151,27 @@ class LightGCN(GeneralRecommender):
         loss_id = self._build_criterion(self.loss_type)
         E0 = self._ego()
         self.restore_user_e, self.restore_item_e = None, None
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int32 [N,3] triples)")
-        triples = torch.as_tensor(data).to(torch.int32).contiguous().to(self.device)
-        n, B = triples.shape[0], int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         out, G, dE0 = torch.empty_like(E0), torch.empty_like(E0), torch.zeros_like(E0)
         gflat = dE0.view(-1)
         optim = ops.DenseOptimizer(opt, self.lr)
         ctx = ops.BprContext(min(B, max(n, 1)), self.factors, self.user_num, self.item_num, device=self.device)
         ctx.set_pointwise(loss_id in ops.POINTWISE_LOSSES)
-        self.epoch_losses, last_loss, step = [], 0.0, 0
+
+        def run_epoch(epoch):
+            order = self._epoch_rows(train_loader, triples, n)
+            ctx.epoch_acc.zero_()
+            for s in range(0, n, B):
+                rows = order[s:s + B]
+                u, i, j = (rows[:, k].contiguous() for k in range(3))
+                self._batch_grads(ctx, E0, out, G, dE0, u, i, j, loss_id)
+                optim.next_step()
+                optim.step(self._flat, gflat)          # also clears the gradient
+            acc = ctx.epoch_acc.cpu()
+            return float(acc[0]), float(acc[1])
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                perm = self._epoch_order(train_loader, triples.shape[0])
-                order = triples[:n] if perm is None else triples[perm[:n].to(self.device)]
-                ctx.epoch_acc.zero_()
-                for s in range(0, n, B):
-                    rows = order[s:s + B]
-                    u, i, j = (rows[:, k].contiguous() for k in range(3))
-                    step += 1
-                    self._batch_grads(ctx, E0, out, G, dE0, u, i, j, loss_id)
-                    optim.next_step()
-                    optim.step(self._flat, gflat)          # also clears the gradient
-                acc = ctx.epoch_acc.cpu()
-                current_loss = float(acc[0])
-                if float(acc[1]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -215,16 +190,7 @@ class LightGCN(GeneralRecommender):
     def rank(self, test_loader):
         """:178-200 -> float32 [n_users, topk] like the reference."""
         ue, ie = self._restore()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).to(self.device)
-            cands_ids = torch.as_tensor(cands_ids).to(self.device)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
-            out.append(ops.mf_rank_topk(ue, ie, us.reshape(-1), cands_ids, self.topk))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+        return self._rank_loader(test_loader, lambda us, cands_ids: ops.mf_rank_topk(ue, ie, us, cands_ids, self.topk))
 
     def full_rank(self, u):
         """:202-210 -> int64 [topk]"""

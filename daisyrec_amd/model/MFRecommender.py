@@ -7,7 +7,6 @@ NeuMF-style consumers of ``.embed_*.weight`` keep working) and methods.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -154,16 +153,9 @@ class MF(GeneralRecommender):
         """MFRecommender.py:106-123.  Returns float32 [n_users, topk] like the reference
         (ids are concatenated onto a float tensor there, MFRecommender.py:107,121)."""
         P, Q = self._tables()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).to(P.device)
-            cands_ids = torch.as_tensor(cands_ids).to(P.device)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
-            out.append(ops.mf_rank_topk(P, Q, us.reshape(-1), cands_ids, self.topk, biases=self._biases()))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+        biases = self._biases()
+        return self._rank_loader(test_loader,
+                                 lambda us, cands_ids: ops.mf_rank_topk(P, Q, us, cands_ids, self.topk, biases=biases))
 
     def full_rank(self, u):
         """MFRecommender.py:126-133 -> int64 [topk]."""

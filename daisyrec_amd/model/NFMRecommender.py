@@ -13,13 +13,13 @@ device's counter-hash masks, not torch's generator: the same distribution, a dif
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender, _tqdm
+from ._flat import flatten_parameters, views_live, views_of
+from .AbstractRecommender import GeneralRecommender
 
 
 class NFM(GeneralRecommender):
@@ -134,16 +134,8 @@ class NFM(GeneralRecommender):
         """Move the parameters into one contiguous device buffer (once), the BatchNorm buffers to the device; returns
         the kernel table of the parameters."""
         self._require_device()
-        if self._flat is None or not self.embed_user.weight.is_cuda:
-            ps = list(self.parameters())
-            flat = torch.empty(sum(p.numel() for p in ps), dtype=torch.float32, device=self.device)
-            off = 0
-            for p in ps:
-                n = p.numel()
-                flat[off:off + n].copy_(p.data.reshape(-1).to(flat.device))
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-            self._flat = flat
+        if not views_live(self._flat, self.parameters()):
+            self._flat = flatten_parameters(self.named_parameters(), self.device)
         for m in self._bn_modules():
             for b in ("running_mean", "running_var", "num_batches_tracked"):
                 if not getattr(m, b).is_cuda:
@@ -151,11 +143,7 @@ class NFM(GeneralRecommender):
         return self._table(dict(self.named_parameters()))
 
     def _grad_table(self, gflat):
-        views, off = {}, 0
-        for name, p in self.named_parameters():
-            views[name] = gflat[off:off + p.numel()].view(p.shape)
-            off += p.numel()
-        return self._table(views)
+        return self._table(views_of(gflat, self.named_parameters()))
 
     def _bn(self):
         mods = self._bn_modules()
@@ -166,10 +154,6 @@ class NFM(GeneralRecommender):
                              self.embed_user.num_embeddings, self.embed_item.num_embeddings, device=self.device)
         ctx.set_path(self.step_path)
         return ctx
-
-    @property
-    def _seed_hi(self):
-        return (int(self.seed) & 0xFFFFFFFF) << 32
 
     def _one_row_check(self, rows):
         if self.batch_norm and self.training and rows == 1:
@@ -241,13 +225,7 @@ class NFM(GeneralRecommender):
         opt = self._resolve_optimizer()
         loss_id = self._build_criterion(self.loss_type)
         p = self._params()
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int32 [N,3] triples)")
-        triples = torch.as_tensor(np.asarray(data)).to(torch.int32).contiguous().to(self.device)
-        n, B = triples.shape[0], int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         if n > 0:
             pw = loss_id in ops.POINTWISE_LOSSES
             self._check_ids(triples[:n, 0], triples[:n, 1] if pw else triples[:n, 1:3].reshape(-1))
@@ -257,37 +235,24 @@ class NFM(GeneralRecommender):
         grads = self._grad_table(gflat)
         optim = ops.DenseOptimizer(opt, self.lr)         # a fresh optimiser per fit, as the reference builds one
         ctx = self._ctx(min(B, max(n, 1)))
-        self.epoch_losses, last_loss = [], 0.0
+
+        def run_epoch(epoch):
+            order = self._epoch_rows(train_loader, triples, n)
+            cols = [order[:, k].contiguous() for k in range(3)]
+            ctx.stats.zero_()
+            m = n - 1 if one_row_tail else n
+            if m > 0:
+                self._steps += ctx.fit_epoch(p, grads, self._bn(), cols[0], cols[1], cols[2], B, optim, self._flat,
+                                             gflat, loss_id, self.reg_1, self.reg_2, dropout=self.dropout,
+                                             seed_hi=self._seed_hi, step0=self._steps)
+            if one_row_tail:
+                torch.cuda.synchronize()
+                self._one_row_check(1)
+            st = ctx.stats.cpu()
+            return float(st[N.NFST_LOSS_SUM]), float(st[N.NFST_NONFINITE])
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                perm = self._epoch_order(train_loader, triples.shape[0])
-                order = triples[:n] if perm is None else triples[perm[:n].to(self.device)]
-                cols = [order[:, k].contiguous() for k in range(3)]
-                ctx.stats.zero_()
-                m = n - 1 if one_row_tail else n
-                if m > 0:
-                    self._steps += ctx.fit_epoch(p, grads, self._bn(), cols[0], cols[1], cols[2], B, optim, self._flat,
-                                                 gflat, loss_id, self.reg_1, self.reg_2, dropout=self.dropout,
-                                                 seed_hi=self._seed_hi, step0=self._steps)
-                if one_row_tail:
-                    torch.cuda.synchronize()
-                    self._one_row_check(1)
-                st = ctx.stats.cpu()
-                current_loss = float(st[N.NFST_LOSS_SUM])
-                if float(st[N.NFST_NONFINITE]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -301,19 +266,14 @@ class NFM(GeneralRecommender):
     def rank(self, test_loader):
         """NFMRecommender.py:160-192 -> float32 [n_users, topk] like the reference."""
         self._params()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).to(self.device).reshape(-1)
-            cands_ids = torch.as_tensor(cands_ids).to(self.device)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
+
+        def topk_of(us, cands_ids):
             Bu, C = cands_ids.shape
             self._check_ids(us, cands_ids)
             scores = self._scores(us, cands_ids.reshape(-1), C_=C)
-            out.append(ops.topk_from_scores(scores.view(Bu, C), cands_ids, self.topk))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+            return ops.topk_from_scores(scores.view(Bu, C), cands_ids, self.topk)
+
+        return self._rank_loader(test_loader, topk_of)
 
     def full_rank(self, u):
         """NFMRecommender.py:194-209 -> int64 [topk]."""

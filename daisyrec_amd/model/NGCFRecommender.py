@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender, _tqdm
+from ._flat import flatten_parameters, views_live, views_of
+from .AbstractRecommender import GeneralRecommender
 
 
 class BiGNN(nn.Module):
@@ -92,26 +93,14 @@ class NGCF(GeneralRecommender):
     def _params(self):
         """Every parameter as a view of ONE flat device buffer (named_parameters order)."""
         self._require_device()
-        if self._flat is None or not self.embed_user.weight.is_cuda:
-            ps = list(self.parameters())
-            flat = torch.empty(sum(p.numel() for p in ps), dtype=torch.float32, device=self.device)
-            off = 0
-            for p in ps:
-                n = p.numel()
-                flat[off:off + n].copy_(p.data.reshape(-1))
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-            self._flat = flat
-            self._gflat = torch.zeros_like(flat)
-            self._grads = {}
-            off = 0
-            for name, p in self.named_parameters():
-                self._grads[name] = self._gflat[off:off + p.numel()].view(p.shape)
-                off += p.numel()
+        if not views_live(self._flat, self.parameters()):
+            self._flat = flatten_parameters(self.named_parameters(), self.device)
+            self._gflat = torch.zeros_like(self._flat)
+            self._grads = views_of(self._gflat, self.named_parameters())
         return self._flat
 
     def _ego(self):
-        self._params()
+        """the [P; Q] rows of the flat buffer `_params` has homed (a step reads them several times: no liveness walk here)"""
         U, I, d = self.user_num, self.item_num, self.embedding_size
         return self._flat[:(U + I) * d].view(U + I, d)
 
@@ -165,6 +154,7 @@ class NGCF(GeneralRecommender):
 
     def forward(self):
         """:158-172 -> (user_all_embeddings [U, D], item_all_embeddings [I, D])"""
+        self._params()
         b = self._work()
         out = torch.empty_like(b["out"])
         X = [torch.empty_like(x) for x in b["X"]]
@@ -258,44 +248,25 @@ class NGCF(GeneralRecommender):
         loss_id = self._build_criterion(self.loss_type)
         flat = self._params()
         self.restore_user_e, self.restore_item_e = None, None
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int32 [N,3] triples)")
-        triples = torch.as_tensor(data).to(torch.int32).contiguous().to(self.device)
-        n, B = triples.shape[0], int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         optim = ops.DenseOptimizer(opt, self.lr)
         ctx, ctx_ego = self._contexts(min(B, max(n, 1)), loss_id)
-        self.epoch_losses, last_loss = [], 0.0
+
+        def run_epoch(epoch):
+            ctx.epoch_acc.zero_()
+            if n > 0:
+                order = self._epoch_rows(train_loader, triples, n)
+                for s in range(0, n, B):
+                    rows = order[s:s + B]
+                    u, i, j = (rows[:, k].contiguous() for k in range(3))
+                    self._batch_grads(ctx, ctx_ego, u, i, j, loss_id)
+                    optim.next_step()
+                    optim.step(flat, self._gflat)          # also clears the gradient
+            acc = ctx.epoch_acc.cpu()
+            return float(acc[0]), float(acc[1])
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                ctx.epoch_acc.zero_()
-                if n > 0:
-                    perm = self._epoch_order(train_loader, triples.shape[0])
-                    order = triples[:n] if perm is None else triples[perm[:n].to(self.device)]
-                    for s in range(0, n, B):
-                        rows = order[s:s + B]
-                        u, i, j = (rows[:, k].contiguous() for k in range(3))
-                        self._batch_grads(ctx, ctx_ego, u, i, j, loss_id)
-                        optim.next_step()
-                        optim.step(flat, self._gflat)          # also clears the gradient
-                acc = ctx.epoch_acc.cpu()
-                current_loss = float(acc[0])
-                if float(acc[1]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -315,16 +286,7 @@ class NGCF(GeneralRecommender):
     def rank(self, test_loader):
         """:221-240 -> float32 [n_users, topk] like the reference."""
         ue, ie = self._restore()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).to(self.device)
-            cands_ids = torch.as_tensor(cands_ids).to(self.device)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
-            out.append(ops.mf_rank_topk(ue, ie, us.reshape(-1), cands_ids, self.topk))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+        return self._rank_loader(test_loader, lambda us, cands_ids: ops.mf_rank_topk(ue, ie, us, cands_ids, self.topk))
 
     def full_rank(self, u):
         """:242-252 -> int64 [topk]"""

@@ -13,13 +13,13 @@ distribution, a different stream; dropout = 0 reproduces the ref
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender, _tqdm
+from ._flat import flatten_parameters, views_live, views_of
+from .AbstractRecommender import GeneralRecommender
 
 
 NEUMF_PRECISIONS = {"fp32": 0, "bf16_inputs": 1, "bf16": 2}     # daisy_neumf_ctx_set_precision levels
@@ -117,25 +117,9 @@ class NeuMF(GeneralRecommender):
         single pass; returns dict name -> view."""
         self._require_device()
         named = self._named()
-        if self._flat is None or not all(p.is_cuda for p in named.values()):
-            total = sum(p.numel() for p in named.values())
-            flat = torch.empty(total, dtype=torch.float32, device=self.device)
-            off = 0
-            for p in named.values():
-                n = p.numel()
-                flat[off:off + n].copy_(p.data.reshape(-1).to(flat.device))
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-            self._flat = flat
+        if not views_live(self._flat, named.values()):
+            self._flat = flatten_parameters(named.items(), self.device)
         return {k: p.data for k, p in named.items()}
-
-    def _views_like_flat(self, flat):
-        out, off = {}, 0
-        for k, p in self._named().items():
-            n = p.numel()
-            out[k] = flat[off:off + n].view(p.shape)
-            off += n
-        return out
 
     def _ctx(self, rows):
         ctx = ops.NeumfContext(rows, self.factors, self.num_layers, self.embed_user_GMF.num_embeddings,
@@ -162,7 +146,7 @@ class NeuMF(GeneralRecommender):
         u, i, j = (torch.as_tensor(x).to(torch.int32).to(self.device).contiguous() for x in batch[:3])
         ctx = self._ctx(2 * u.numel())
         try:
-            scratch = self._views_like_flat(torch.zeros_like(self._flat))
+            scratch = views_of(torch.zeros_like(self._flat), self._named().items())
             ctx.step_grads(p, scratch, u, i, j, loss_id, self.reg_1, self.reg_2,
                            dropout=self.dropout if self.training else 0.0, seed=self.seed)
             return ctx.stats[N.NST_LOSS].clone()
@@ -175,47 +159,30 @@ class NeuMF(GeneralRecommender):
         opt = self._resolve_optimizer()
         loss_id = self._build_criterion(self.loss_type)
         p = self._params()
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over BasicDataset (dataset.data = int32 [N,3] triples)")
-        triples = torch.as_tensor(data).to(torch.int32).contiguous().to(self.device)
-        n, B = triples.shape[0], int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        triples, n, B = self._train_rows(train_loader)
         gflat = torch.zeros_like(self._flat)
-        grads = self._views_like_flat(gflat)
+        grads = views_of(gflat, self._named().items())
         optim = ops.DenseOptimizer(opt, self.lr)
         ctx = self._ctx(2 * min(B, max(n, 1)))
-        self.epoch_losses, last_loss, step = [], 0.0, 0
+        step = 0
+
+        def run_epoch(epoch):
+            nonlocal step
+            order = self._epoch_rows(train_loader, triples, n)
+            # the epoch's ids column by column, once: a batch is then three views (at B = 256 the three per-batch copies
+            # were 3 of the step's ~46 launches, each a few microseconds of latency)
+            cols = [order[:, k].contiguous() for k in range(3)]
+            # (the epoch's loss: every step adds its loss to stats[NST_LOSS_SUM] on the device - no launch per step for it)
+            ctx.stats[N.NST_LOSS_SUM:N.NST_LOSS_SUM + 1].zero_()
+            # the loop over the batches (zero_grad / calc_loss / backward / optimizer.step: step k uses the dropout seed
+            # (self.seed << 32) | k) runs in the library: at 256 samples a step is ~40 us of kernels, less than the
+            # Python of one iteration around two library calls
+            step += ctx.fit_epoch(p, grads, cols[0], cols[1], cols[2], B, optim, self._flat, gflat, loss_id, self.reg_1,
+                                  self.reg_2, dropout=self.dropout, seed_hi=self._seed_hi, step0=step)
+            return float(ctx.stats[N.NST_LOSS_SUM].cpu()), 0.0      # (no counter: a non-finite step loss shows in the sum)
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                perm = self._epoch_order(train_loader, triples.shape[0])
-                order = triples[:n] if perm is None else triples[perm[:n].to(self.device)]
-                # the epoch's ids column by column, once: a batch is then three views (at B = 256 the three per-batch copies
-                # were 3 of the step's ~46 launches, each a few microseconds of latency)
-                cols = [order[:, k].contiguous() for k in range(3)]
-                # (the epoch's loss: every step adds its loss to stats[NST_LOSS_SUM] on the device - no launch per step for it)
-                ctx.stats[N.NST_LOSS_SUM:N.NST_LOSS_SUM + 1].zero_()
-                # the loop over the batches (zero_grad / calc_loss / backward / optimizer.step: step k uses the dropout seed
-                # (self.seed << 32) | k) runs in the library: at 256 samples a step is ~40 us of kernels, less than the
-                # Python of one iteration around two library calls
-                step += ctx.fit_epoch(p, grads, cols[0], cols[1], cols[2], B, optim, self._flat, gflat, loss_id, self.reg_1,
-                                      self.reg_2, dropout=self.dropout, seed_hi=(int(self.seed) & 0xFFFFFFFF) << 32, step0=step)
-                current_loss = float(ctx.stats[N.NST_LOSS_SUM].cpu())
-                if current_loss != current_loss or current_loss in (float("inf"), float("-inf")):
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -227,24 +194,20 @@ class NeuMF(GeneralRecommender):
     def rank(self, test_loader):
         """NeuMFRecommender.py:178-209 -> float32 [n_users, topk] like the reference."""
         p = self._params()
-        out, ctx = [], None
+        ctxs = []
+
+        def topk_of(us, cands_ids):
+            Bu, C = cands_ids.shape
+            if not ctxs:
+                ctxs.append(self._ctx(min(Bu * C, 1 << 18)))
+            scores = ctxs[0].scores(p, us, cands_ids.reshape(-1), C_=C)
+            return ops.topk_from_scores(scores.view(Bu, C), cands_ids, self.topk)
+
         try:
-            for us, cands_ids in test_loader:
-                us = torch.as_tensor(us).to(self.device).reshape(-1)
-                cands_ids = torch.as_tensor(cands_ids).to(self.device)
-                if cands_ids.dim() == 1:
-                    cands_ids = cands_ids.unsqueeze(0)
-                Bu, C = cands_ids.shape
-                if ctx is None:
-                    ctx = self._ctx(min(Bu * C, 1 << 18))
-                scores = ctx.scores(p, us, cands_ids.reshape(-1), C_=C)
-                out.append(ops.topk_from_scores(scores.view(Bu, C), cands_ids, self.topk))
+            return self._rank_loader(test_loader, topk_of)
         finally:
-            if ctx is not None:
+            for ctx in ctxs:
                 ctx.close()
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
 
     def full_rank(self, u):
         """NeuMFRecommender.py:211-233 -> int64 [topk]."""

@@ -14,13 +14,13 @@ the device's counter hash, not torch's generator: the same distributions, a diff
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import AERecommender, _tqdm
+from ._flat import flatten_parameters, views_live
+from .AbstractRecommender import AERecommender
 
 
 class VAECF(AERecommender):
@@ -75,34 +75,11 @@ class VAECF(AERecommender):
         return nn.Sequential(*mods)
 
     # -- parameters as the kernels see them: ONE flat device buffer, the module's tensors are views -------------------
-    def _flat_views_live(self):
-        if self._flat is None:
-            return False
-        off, base = 0, self._flat.data_ptr()
-        for p in self.parameters():
-            if not p.is_cuda or p.data_ptr() != base + 4 * off:
-                return False
-            off += p.numel()
-        return True
-
     def _params(self):
         """Move the parameters into one contiguous device buffer (once; encoder.0.weight item-major), return it."""
         self._require_device()
-        if not self._flat_views_live():
-            ps = list(self.named_parameters())
-            flat = torch.empty(sum(p.numel() for _, p in ps), dtype=torch.float32, device=self.device)
-            off = 0
-            for name, p in ps:
-                n = p.numel()
-                if name == "encoder.0.weight":
-                    h, I = p.shape
-                    flat[off:off + n].view(I, h).copy_(p.data.t())
-                    p.data = flat[off:off + n].view(I, h).t()
-                else:
-                    flat[off:off + n].copy_(p.data.reshape(-1))
-                    p.data = flat[off:off + n].view(p.shape)
-                off += n
-            self._flat = flat
+        if not views_live(self._flat, self.parameters()):
+            self._flat = flatten_parameters(self.named_parameters(), self.device, transposed=("encoder.0.weight",))
         return self._flat
 
     def _csr(self):
@@ -116,10 +93,6 @@ class VAECF(AERecommender):
             lens = (csr[0][1:] - csr[0][:-1]).cpu()
             self._csr_cache = (key, csr, lens)
         return self._csr_cache[1], self._csr_cache[2]
-
-    @property
-    def _seed_hi(self):
-        return (int(self.seed) & 0xFFFFFFFF) << 32
 
     def _check_users(self, users):
         U = int(self.history_item_id.shape[0])
@@ -202,49 +175,29 @@ class VAECF(AERecommender):
         opt = self._resolve_optimizer()
         W = self._params()
         csr, lens = self._csr()
-        data = getattr(train_loader.dataset, "data", None)
-        if data is None:
-            raise TypeError("fit expects a DataLoader over AEDataset (dataset.data = the training users)")
-        users_all = torch.as_tensor(np.asarray(data)).reshape(-1).to(torch.int64)
-        n, B = users_all.numel(), int(train_loader.batch_size)
-        if train_loader.drop_last:
-            n = (n // B) * B
+        users_all, n, B = self._train_rows(train_loader, columns=1, expects="AEDataset (dataset.data = the training users)")
         self._check_users(users_all[:n])
         ulens = lens[users_all]
         max_entries = int(torch.topk(ulens, min(B, ulens.numel())).values.sum()) if ulens.numel() else 0
         g = torch.zeros_like(W)
         optim = ops.DenseOptimizer(opt, self.lr)         # a fresh optimiser per fit, as the reference builds one
         ctx = self._ctx(min(B, max(n, 1)), max_entries)
-        self.epoch_losses, last_loss = [], 0.0
+
+        def run_epoch(epoch):
+            order = self._epoch_rows(train_loader, users_all, n)      # (drop_last: the order's first n positions)
+            ctx.stats.zero_()
+            if n > 0:
+                entries = [int(x.sum()) for x in torch.split(lens[order], B)]
+                steps = ctx.fit_epoch(W, g, csr, order.to(self.device), B, entries, optim, self.dropout,
+                                      self.anneal_cap, self.total_anneal_steps, self.update,
+                                      seed_hi=self._seed_hi, step0=self._steps)
+                self._steps += steps
+                self.update += steps
+            st = ctx.stats.cpu()
+            return float(st[N.VST_LOSS_SUM]), float(st[N.VST_NONFINITE])
+
         try:
-            epochs = range(1, self.epochs + 1)
-            bar = _tqdm(epochs) if (_tqdm is not None and self.show_progress) else None
-            for epoch in (bar if bar is not None else epochs):
-                self.train()
-                perm = self._epoch_order(train_loader, users_all.numel())      # (drop_last: its first n positions)
-                order = users_all[:n] if perm is None else users_all[perm[:n]]
-                ctx.stats.zero_()
-                if n > 0:
-                    ol = lens[order]
-                    entries = [int(x.sum()) for x in torch.split(ol, B)]
-                    steps = ctx.fit_epoch(W, g, csr, order.to(self.device), B, entries, optim, self.dropout,
-                                          self.anneal_cap, self.total_anneal_steps, self.update,
-                                          seed_hi=self._seed_hi, step0=self._steps)
-                    self._steps += steps
-                    self.update += steps
-                st = ctx.stats.cpu()
-                current_loss = float(st[N.VST_LOSS_SUM])
-                if float(st[N.VST_NONFINITE]) > 0 or current_loss != current_loss:
-                    raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-                self.epoch_losses.append(current_loss)
-                if bar is not None:
-                    bar.set_description(f"[Epoch {epoch:03d}]")
-                    bar.set_postfix(loss=current_loss)
-                self.eval()
-                if abs(current_loss - last_loss) < 1e-5 and self.early_stop:
-                    self.logger.info("Satisfy early stop mechanism")
-                    break
-                last_loss = current_loss
+            self._run_epochs(run_epoch)
         finally:
             torch.cuda.synchronize()
             ctx.close()
@@ -259,19 +212,13 @@ class VAECF(AERecommender):
         """VAECFRecommender.py:121-138 -> float32 [n_users, topk] like the reference; only the candidates' rows of the
         last layer are evaluated."""
         self._params()
-        out = []
-        for us, cands_ids in test_loader:
-            us = torch.as_tensor(us).reshape(-1)
-            cands_ids = torch.as_tensor(cands_ids).to(torch.int64)
-            if cands_ids.dim() == 1:
-                cands_ids = cands_ids.unsqueeze(0)
+
+        def topk_of(us, cands_ids):
+            cands_ids = cands_ids.to(torch.int64)
             self._check_items(cands_ids)
-            cands_dev = cands_ids.to(self.device)
-            scores = self._scores(us, cands_dev)
-            out.append(ops.topk_from_scores(scores, cands_dev, self.topk))
-        if not out:
-            return np.zeros((0,), dtype=np.float32)
-        return torch.cat(out, 0).to(torch.float32).cpu().numpy()
+            return ops.topk_from_scores(self._scores(us, cands_ids), cands_ids, self.topk)
+
+        return self._rank_loader(test_loader, topk_of)
 
     def full_rank(self, u):
         """VAECFRecommender.py:140-145 -> int64 [topk] over all items (training items included)."""

@@ -68,10 +68,38 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
-class TrainIndex:
+class _Native:
+    """Owner of one native handle (`_h`).  A subclass names the library's destroy function and, where there is one, its
+    bytes function.  close() may be called twice, and after a constructor that failed before the handle was set; the
+    object is not usable after it."""
+
+    _destroy = None
+    _bytes = None
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            check(type(self)._destroy(h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def nbytes(self):
+        return int(type(self)._bytes(self._h))
+
+
+class TrainIndex(_Native):
     """Owner of a native ``daisy_train_index``: the training triples in CSR order + their item entries
     sorted by item, built once per fit (BasicDataset's triple array is immutable, dataset.py:21).
     Raises ValueError when an id lies outside the tables (the reference: IndexError in nn.Embedding)."""
+
+    _destroy = lib.daisy_train_index_destroy
+    _bytes = lib.daisy_train_index_bytes
 
     def __init__(self, triples, user_num: int, item_num: int, user_base: int = 0, user_sorted=None, pointwise=False):
         """pointwise: rows are (user, item, label) (CL / SL, sampler.py:93-98): one item entry per row"""
@@ -87,25 +115,12 @@ class TrainIndex:
                                                (N.PLAN_TRIPLES_USER_SORTED if user_sorted else 0)
                                                | (N.PLAN_POINTWISE if pointwise else 0), _stream()))
 
-    @property
-    def nbytes(self):
-        return int(lib.daisy_train_index_bytes(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            check(lib.daisy_train_index_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EpochPlan:
+class EpochPlan(_Native):
     """Owner of a native ``daisy_epoch_plan``: one epoch laid out batch by batch in HBM
     (replaces a pass over DataLoader(BasicDataset(triples)), dataset.py:5-27)."""
+
+    _destroy = lib.daisy_epoch_plan_destroy
+    _bytes = lib.daisy_epoch_plan_bytes
 
     def __init__(self, max_triples: int, user_num: int, item_num: int, device="cuda"):
         self.device = torch.device(device)
@@ -176,21 +191,6 @@ class EpochPlan:
         b = B.value
         return u[:b], i[:b], j[:b], ei[:2 * b], es[:2 * b], eu[:2 * b]
 
-    @property
-    def nbytes(self):
-        return int(lib.daisy_epoch_plan_bytes(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            check(lib.daisy_epoch_plan_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def triples_user_sorted(triples) -> bool:
     """One-off check (plumbing, not the hot path) that a device triple array is in CSR order."""
@@ -216,8 +216,11 @@ def feistel_positions_at(ids, n, seed, epoch=0):
     return out
 
 
-class BprContext:
+class BprContext(_Native):
     """Owner of a native ``daisy_bpr_ctx`` (per-step scratch on one GPU)."""
+
+    _destroy = lib.daisy_bpr_ctx_destroy
+    _bytes = lib.daisy_bpr_ctx_scratch_bytes
 
     def __init__(self, max_batch: int, d: int, user_num: int, item_num: int, device="cuda"):
         self.max_batch, self.d, self.user_num, self.item_num = int(max_batch), int(d), int(user_num), int(item_num)
@@ -310,20 +313,7 @@ class BprContext:
         reduced entry counts and the finalized global norms); clears g_rows and cnt_rows."""
         item_apply_counts(Q_rows, g_rows, cnt_rows, lr, reg_1, reg_2, self.stats)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            check(lib.daisy_bpr_ctx_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def scratch_bytes(self):
-        return int(lib.daisy_bpr_ctx_scratch_bytes(self._h))
+    scratch_bytes = _Native.nbytes
 
     def set_pointwise(self, flag):
         """Rows given to set_batch* are (user, item, label) - the CL / SL layout (sampler.py:93-98)."""
@@ -482,6 +472,15 @@ class DenseOptimizer:
         if st is None:
             st = self._state[W.data_ptr()] = tuple(torch.zeros_like(W) for _ in range(2 if self.kind == "adam" else 1))
         return st
+
+    def native_args(self, W, g=None):
+        """The optimiser as the library's fit_epoch entries take it: (kind index, lr, [W, g,] state0 or NULL, state1 or
+        NULL) for the flat vectors W / g (g=None: an entry that takes W and g elsewhere in its signature)."""
+        f = torch.float32
+        st = self.state_for(W)
+        vectors = (_ptr(W, f, "W"), _ptr(g, f, "g")) if g is not None else ()
+        return (self.KINDS.index(self.kind), self.lr) + vectors + tuple(
+            _ptr(st[k], f, f"state{k}") if len(st) > k else None for k in range(2))
 
     def step(self, W, g):
         W, g = W.view(-1), g.view(-1)
@@ -833,8 +832,11 @@ def _neumf_table(tensors, num_layers):
     return t
 
 
-class NeumfContext:
+class NeumfContext(_Native):
     """Activation workspace + entry points of the NeuMF path (daisy_neumf_*)."""
+
+    _destroy = lib.daisy_neumf_ctx_destroy
+    _bytes = lib.daisy_neumf_ctx_bytes
 
     def __init__(self, max_rows, factors, num_layers, user_num, item_num, model="NeuMF", device=None):
         if model not in NEUMF_MODELS:
@@ -847,17 +849,6 @@ class NeumfContext:
                                              NEUMF_MODELS[model], int(user_num), int(item_num)))
         self.max_rows = int(max_rows)
         self.stats = torch.zeros(N.NEUMF_STATS_LEN, dtype=torch.float64, device=self.device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.daisy_neumf_ctx_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    @property
-    def nbytes(self):
-        return int(lib.daisy_neumf_ctx_bytes(self._h))
 
     def set_precision(self, bf16_gemm):
         """0 / False (default): exact fp32; 1 / True: bf16-input MFMA in the MLP tower (fp32 operands rounded on the way
@@ -897,16 +888,11 @@ class NeumfContext:
         if optim.t != int(step0):
             raise ValueError(f"fit_epoch: the optimiser has taken {optim.t} steps, step0 = {step0}")
         W, g = W.view(-1), g.view(-1)
-        st = optim.state_for(W)
         pt, gt = _neumf_table(params, self.L), _neumf_table(grads, self.L)
-        f = torch.float32
         check(lib.daisy_neumf_fit_epoch(self._h, C.byref(pt), C.byref(gt), _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"),
                                         _ptr(j, torch.int32, "j"), n, int(batch), int(loss_type), float(gamma), float(reg_1),
-                                        float(reg_2), float(dropout), int(seed_hi), int(step0),
-                                        DenseOptimizer.KINDS.index(optim.kind), float(optim.lr), _ptr(W, f, "W"), _ptr(g, f, "g"),
-                                        _ptr(st[0], f, "state0") if len(st) > 0 else None,
-                                        _ptr(st[1], f, "state1") if len(st) > 1 else None, W.numel(),
-                                        _ptr(self.stats, torch.float64, "stats"), _stream()))
+                                        float(reg_2), float(dropout), int(seed_hi), int(step0), *optim.native_args(W, g),
+                                        W.numel(), _ptr(self.stats, torch.float64, "stats"), _stream()))
         optim.t += steps
         return steps
 
@@ -973,9 +959,12 @@ def gemm_nt(A, B, bf16=False):
 # ------------------------------------------------------------------------------------------------
 # LightGCN (LightGCNRecommender.py) - see include/daisyrec_amd.h
 # ------------------------------------------------------------------------------------------------
-class LgcnGraph:
+class LgcnGraph(_Native):
     """Normalised adjacency A_hat = D^-1/2 A D^-1/2 of the user-item graph on the device
     (LightGCNRecommender.py:74-107) and the products built on it."""
+
+    _destroy = lib.daisy_lgcn_graph_destroy
+    _bytes = lib.daisy_lgcn_graph_bytes
 
     def __init__(self, users, items, user_num, item_num):
         users = users.to(torch.int32).contiguous()
@@ -990,17 +979,6 @@ class LgcnGraph:
                                               _stream()))
         self.nnz = int(lib.daisy_lgcn_graph_nnz(self._h))
         self._work = None
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.daisy_lgcn_graph_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    @property
-    def nbytes(self):
-        return int(lib.daisy_lgcn_graph_bytes(self._h))
 
     def set_reproducible(self, flag):
         """True: row-owner products (bitwise reproducible); False (default): chunked segmented reduction."""
@@ -1180,8 +1158,11 @@ def _nfm_bn(bn, num_layers):
     return st
 
 
-class NfmContext:
+class NfmContext(_Native):
     """Activation workspace + entry points of the NFM path (daisy_nfm_*)."""
+
+    _destroy = lib.daisy_nfm_ctx_destroy
+    _bytes = lib.daisy_nfm_ctx_bytes
 
     def __init__(self, max_rows, factors, num_layers, act, batch_norm, user_num, item_num, device=None):
         self.device = torch.device(device if device is not None else "cuda")
@@ -1193,17 +1174,6 @@ class NfmContext:
                                            int(user_num), int(item_num)))
         self.max_rows = int(max_rows)
         self.stats = torch.zeros(N.NFM_STATS_LEN, dtype=torch.float64, device=self.device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.daisy_nfm_ctx_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    @property
-    def nbytes(self):
-        return int(lib.daisy_nfm_ctx_bytes(self._h))
 
     def set_path(self, path):
         """'auto' (the layered step), 'small' (the one-workgroup step, B <= NFM_SMALL_MAX_B) or 'layered': same bits."""
@@ -1240,15 +1210,11 @@ class NfmContext:
         n = int(u.numel())
         steps = (n + int(batch) - 1) // int(batch)
         W, g = W.view(-1), g.view(-1)
-        st = optim.state_for(W)
         pt, gt, bt = _nfm_table(params, self.L, self.bn), _nfm_table(grads, self.L, self.bn), _nfm_bn(bn, self.L)
-        f = torch.float32
         check(lib.daisy_nfm_fit_epoch(self._h, C.byref(pt), C.byref(gt), C.byref(bt), _ptr(u, torch.int32, "u"),
                                       _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), n, int(batch), int(loss_type),
                                       float(gamma), float(reg_1), float(reg_2), float(dropout), int(seed_hi) & (2 ** 64 - 1),
-                                      int(step0), int(optim.t), DenseOptimizer.KINDS.index(optim.kind), float(optim.lr), _ptr(W, f, "W"),
-                                      _ptr(g, f, "g"), _ptr(st[0], f, "state0") if len(st) > 0 else None,
-                                      _ptr(st[1], f, "state1") if len(st) > 1 else None, W.numel(),
+                                      int(step0), int(optim.t), *optim.native_args(W, g), W.numel(),
                                       _ptr(self.stats, torch.float64, "stats"), _stream()))
         optim.t += steps
         return steps
@@ -1290,9 +1256,12 @@ def vae_history_csr(history_item_id, history_item_value, item_num):
     return row_ptr, item[keep].to(torch.int32).contiguous(), v[keep].contiguous()
 
 
-class VaeContext:
+class VaeContext(_Native):
     """Workspace + entry points of the Multi-VAE path (daisy_vae_*): layer widths, the batch capacity and the flat
     parameter layout (encoder.0.weight item-major)."""
+
+    _destroy = lib.daisy_vae_ctx_destroy
+    _bytes = lib.daisy_vae_ctx_bytes
 
     def __init__(self, max_batch, max_entries, item_num, hidden, latent_dim, device=None):
         self.device = torch.device(device if device is not None else "cuda")
@@ -1304,17 +1273,6 @@ class VaeContext:
                                            len(self.hidden), hid, int(latent_dim)))
         self.max_batch, self.max_entries, self.item_num = int(max_batch), int(max_entries), int(item_num)
         self.stats = torch.zeros(N.VAE_STATS_LEN, dtype=torch.float64, device=self.device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.daisy_vae_ctx_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    @property
-    def nbytes(self):
-        return int(lib.daisy_vae_ctx_bytes(self._h))
 
     @property
     def param_count(self):
@@ -1347,14 +1305,11 @@ class VaeContext:
         steps = (n + int(batch) - 1) // int(batch)
         ent = (C.c_int64 * steps)(*[int(x) for x in entries])
         W, g = W.view(-1), g.view(-1)
-        st = optim.state_for(W)
         f = torch.float32
         check(lib.daisy_vae_fit_epoch(self._h, _ptr(W, f, "W"), _ptr(g, f, "g"), rp, cp, vp, U,
                                       _ptr(users, torch.int64, "users"), n, int(batch), ent, float(dropout),
                                       float(anneal_cap), int(total_anneal_steps), int(update0), int(seed_hi) & (2 ** 64 - 1),
-                                      int(step0), int(optim.t), DenseOptimizer.KINDS.index(optim.kind), float(optim.lr),
-                                      _ptr(st[0], f, "state0") if len(st) > 0 else None,
-                                      _ptr(st[1], f, "state1") if len(st) > 1 else None,
+                                      int(step0), int(optim.t), *optim.native_args(W),
                                       _ptr(self.stats, torch.float64, "stats"), _stream()))
         optim.t += steps
         return steps
