@@ -105,8 +105,8 @@ struct daisy_train_index {
 //   kind 1 (partitioned, daisy_epoch_plan_build_indexed): plain SoA records, 32 B per interaction; staged step only
 struct daisy_epoch_plan {
     int64_t max_triples, U, I;
-    void *arena;          // kind 0 buffers (allocated by the first daisy_epoch_plan_build)
-    size_t arena_bytes, temp_bytes;
+    daisy::DeviceArena arena;    // kind 0 buffers (allocated by the first daisy_epoch_plan_build)
+    size_t temp_bytes;
     // double buffers of the two radix sorts
     uint32_t *k32[2];     // [2n] 32-bit keys
     uint64_t *k64[2];     // [2n] 64-bit keys (only when batch bits + id bits > 32)
@@ -157,8 +157,7 @@ constexpr int64_t kMergeMaxBatch = 131072;   // largest batch of the three-launc
 struct daisy_bpr_ctx {
     int64_t max_batch, U, I;
     int d;
-    void *arena;
-    size_t arena_bytes;
+    daisy::DeviceArena arena;
     float2 *coef;        // (dL/dpos, dL/dneg) per sample   [max_batch]
     double *partials;    // per-workgroup sums              [kMaxGrid*8], then [kPreBlocks] of the staged step's
                          // pre-norm pass (k_unorm), which the user pass reads while it writes the first part
@@ -311,7 +310,7 @@ __device__ __forceinline__ void reduce_partials_block(const double *__restrict__
 }
 
 
-// torch.optim.Adam single-tensor math on one row fragment: the expressions of k_adam_dense (bpr_train.hip), shared by the
+// torch.optim.Adam single-tensor math on one row fragment: the expressions of k_adam_dense (dense_opt.hip), shared by the
 // lazy row updates there and by the row owners of the staged step
 template <class C>
 __device__ __forceinline__ void adam_row(Row<C> &w, Row<C> &m, Row<C> &v, const Row<C> &g, float step_size, float bc2_sqrt,

@@ -98,7 +98,6 @@ constexpr int kItemWinFloats = DAISY_ITEM_WINF;     // 24 KB of Q rows per workg
 constexpr int kStagedUserBlock = 128, kStagedItemBlock = DAISY_ITEM_BLK;    // threads per workgroup of the two passes (measured:
                                                                  // user pass 387 -> 360 us at 128, item pass indifferent)
 
-static inline hipStream_t S(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // =============================================================================
 // partitioned epoch plan
@@ -2399,7 +2398,7 @@ int daisy_train_index_create(daisy_train_index **out, const int32_t *triples, in
                     (long long)n_triples);
     DAISY_CHECK_ARG(user_num > 0 && user_num <= INT32_MAX && item_num > 0 && item_num < ((int64_t)1 << 30),
                     "train_index_create: user_num/item_num out of range");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t n = n_triples;
     const bool sorted = (flags & DAISY_PLAN_TRIPLES_USER_SORTED) != 0;
     const int pointwise = (flags & DAISY_PLAN_POINTWISE) ? 1 : 0;
@@ -2513,7 +2512,7 @@ int daisy_epoch_plan_build_indexed(daisy_epoch_plan *plan, const daisy_train_ind
                     "epoch_plan_build_indexed: bad order_mode %d", order_mode);
     DAISY_CHECK_ARG(order_mode != DAISY_ORDER_PERM || perm != nullptr,
                     "epoch_plan_build_indexed: DAISY_ORDER_PERM needs perm");
-    return plan_build_partitioned(plan, index, perm, order_mode, seed, epoch, batch_size, 0, S(stream));
+    return plan_build_partitioned(plan, index, perm, order_mode, seed, epoch, batch_size, 0, as_stream(stream));
 }
 
 int daisy_epoch_plan_build_positions(daisy_epoch_plan *plan, const daisy_train_index *index, const int64_t *positions,
@@ -2525,7 +2524,7 @@ int daisy_epoch_plan_build_positions(daisy_epoch_plan *plan, const daisy_train_i
     DAISY_CHECK_ARG(batch_size > 0 && batch_size < ((int64_t)1 << 31), "epoch_plan_build_positions: bad batch_size");
     DAISY_CHECK_ARG(n_total >= index->n && n_total < ((int64_t)1 << 32),
                     "epoch_plan_build_positions: n_total=%lld must be in [n, 2^32)", (long long)n_total);
-    return plan_build_partitioned(plan, index, positions, DAISY_ORDER_PERM, 0, 0, batch_size, n_total, S(stream));
+    return plan_build_partitioned(plan, index, positions, DAISY_ORDER_PERM, 0, 0, batch_size, n_total, as_stream(stream));
 }
 
 int64_t daisy_epoch_plan_batch_rows(const daisy_epoch_plan *plan, int64_t k) {
@@ -2552,7 +2551,7 @@ int daisy_bpr_ctx_set_p_stream(daisy_bpr_ctx *ctx, int32_t mode) {
 int daisy_bpr_staged_prenorm(daisy_bpr_ctx *ctx, const float *P, double *stats, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && P && stats, "staged_prenorm: NULL argument");
     if (!ctx->batch_set) { set_error("staged_prenorm: no batch set"); return DAISY_ERR_STATE; }
-    return staged_prenorm(ctx, P, stats, true, nullptr, S(stream));
+    return staged_prenorm(ctx, P, stats, true, nullptr, as_stream(stream));
 }
 
 int daisy_bpr_staged_user(daisy_bpr_ctx *ctx, float *P, const float *Q, int32_t loss_type, float gamma, float lr,
@@ -2565,8 +2564,8 @@ int daisy_bpr_staged_user(daisy_bpr_ctx *ctx, float *P, const float *Q, int32_t 
         return DAISY_ERR_STATE;
     }
     int gu = 0;
-    if ((rc = staged_user(ctx, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, &gu, 0, false, nullptr, nullptr, S(stream)))) return rc;
-    return launch_reduce_partials(ctx->partials, gu, stats, false, 0.f, 0.f, nullptr, nullptr, S(stream));
+    if ((rc = staged_user(ctx, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, &gu, 0, false, nullptr, nullptr, as_stream(stream)))) return rc;
+    return launch_reduce_partials(ctx->partials, gu, stats, false, 0.f, 0.f, nullptr, nullptr, as_stream(stream));
 }
 
 int daisy_bpr_staged_item(daisy_bpr_ctx *ctx, int32_t loss_type, float *Q, float *gQ, float *cnt, float lr,
@@ -2575,7 +2574,7 @@ int daisy_bpr_staged_item(daisy_bpr_ctx *ctx, int32_t loss_type, float *Q, float
                     "staged_item: give either Q (apply in place) or gQ + cnt (gradient output)");
     int rc = staged_check(ctx, loss_type, "staged_item");
     if (rc) return rc;
-    return staged_item(ctx, loss_type, Q ? Q : gQ, cnt, Q != nullptr, lr, reg_1, reg_2, stats, S(stream));
+    return staged_item(ctx, loss_type, Q ? Q : gQ, cnt, Q != nullptr, lr, reg_1, reg_2, stats, as_stream(stream));
 }
 
 int daisy_bpr_staged_item_slices(daisy_bpr_ctx *ctx, const int32_t *item_bounds, int32_t n_slices, daisy_stream_t stream) {
@@ -2590,7 +2589,7 @@ int daisy_bpr_staged_item_slices(daisy_bpr_ctx *ctx, const int32_t *item_bounds,
     }
     DAISY_CHECK_ARG(item_bounds[0] == 0 && item_bounds[n_slices] >= ctx->I,
                     "staged_item_slices: the slices must cover the items 0..%lld", (long long)ctx->I);
-    hipLaunchKernelGGL(k_slice_ranges, dim3(1), dim3(64), 0, S(stream), ctx->sv, sb, (int)n_slices, ctx->slice_rng);
+    hipLaunchKernelGGL(k_slice_ranges, dim3(1), dim3(64), 0, as_stream(stream), ctx->sv, sb, (int)n_slices, ctx->slice_rng);
     DAISY_LAUNCH_CHECK();
     ctx->n_slices = n_slices;
     return DAISY_OK;
@@ -2603,7 +2602,7 @@ int daisy_bpr_staged_item_slice(daisy_bpr_ctx *ctx, int32_t loss_type, float *gQ
     if (rc) return rc;
     DAISY_CHECK_ARG(slice >= 0 && slice < ctx->n_slices, "staged_item_slice: slice %d of %d (daisy_bpr_staged_item_slices first)",
                     slice, ctx->n_slices);
-    return staged_item(ctx, loss_type, gQ, cnt, false, lr, reg_1, reg_2, stats, S(stream), slice);
+    return staged_item(ctx, loss_type, gQ, cnt, false, lr, reg_1, reg_2, stats, as_stream(stream), slice);
 }
 
 int daisy_bpr_staged_adam_step(daisy_bpr_ctx *ctx, float *P, float *Q, int32_t loss_type, float gamma, float lr,
@@ -2625,7 +2624,7 @@ int daisy_bpr_staged_adam_step(daisy_bpr_ctx *ctx, float *P, float *Q, int32_t l
         return DAISY_ERR_ARG;
     }
     return staged_adam_step(ctx, P, Q, loss_type, gamma, reg_1, reg_2, a, table, bias_grad_out, stats, epoch_acc,
-                            step_loss, S(stream));
+                            step_loss, as_stream(stream));
 }
 
 // The epoch loop of GeneralRecommender.fit (AbstractRecommender.py:118-128) with torch.optim.Adam
@@ -2653,7 +2652,7 @@ int daisy_bpr_fit_epoch_adam(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, f
         // inside one persistent workgroup, like the SGD epoch (csrc/bpr_small.hip) - 48 -> ~12 us per step at B = 256
         DAISY_CHECK_ARG(plan->U == ctx->U && plan->I == ctx->I, "fit_epoch_adam: plan does not fit the context");
         SmallAdamArgs ad{mP, vP, lastP, mQ, vQ, lastQ, table, beta1, beta2, eps, first_step};
-        int rc = small_fit_epoch(ctx, plan, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, epoch_acc, step_losses, S(stream), &ad);
+        int rc = small_fit_epoch(ctx, plan, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, epoch_acc, step_losses, as_stream(stream), &ad);
         if (rc) return rc;
     } else {
         if (plan->kind == 0) {
@@ -2694,7 +2693,7 @@ int daisy_bpr_staged_adam_catchup_users(daisy_bpr_ctx *ctx, float *P, float *mP,
     if (!ctx->batch_set) { set_error("staged_adam_catchup_users: no batch set"); return DAISY_ERR_STATE; }
     StagedAdam a = adam_consts(0.f, beta1, beta2, eps, step);
     a.mP = mP; a.vP = vP; a.lastP = lastP;
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const StreamView &v = ctx->sv;
     const int d = ctx->d;
     int rc = dispatch_d(d, [&](auto cfg) {
@@ -2727,8 +2726,8 @@ int daisy_bpr_staged_user_adam(daisy_bpr_ctx *ctx, float *P, const float *Q, int
     StagedAdam a = adam_consts(lr, beta1, beta2, eps, step);
     a.mP = mP; a.vP = vP; a.lastP = lastP;
     int gu = 0;
-    if ((rc = staged_user(ctx, P, Q, loss_type, gamma, 0.f, reg_1, reg_2, stats, &gu, 0, false, nullptr, nullptr, S(stream), &a))) return rc;
-    return launch_reduce_partials(ctx->partials, gu, stats, false, 0.f, 0.f, nullptr, nullptr, S(stream));
+    if ((rc = staged_user(ctx, P, Q, loss_type, gamma, 0.f, reg_1, reg_2, stats, &gu, 0, false, nullptr, nullptr, as_stream(stream), &a))) return rc;
+    return launch_reduce_partials(ctx->partials, gu, stats, false, 0.f, 0.f, nullptr, nullptr, as_stream(stream));
 }
 
 int daisy_item_apply_counts_adam(float *Q, float *g, float *cnt, float *m, float *v, int64_t rows, int32_t d, float lr,
@@ -2740,7 +2739,7 @@ int daisy_item_apply_counts_adam(float *Q, float *g, float *cnt, float *m, float
     int rc = dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         hipLaunchKernelGGL((k_item_apply_counts_adam<C>), dim3(grid_for(rows, C::GROUPS_PER_BLOCK * 2)), dim3(kBlock), 0,
-                           S(stream), Q, g, cnt, m, v, rows, (int)d, reg_1, reg_2, opt, stats);
+                           as_stream(stream), Q, g, cnt, m, v, rows, (int)d, reg_1, reg_2, opt, stats);
         return DAISY_OK;
     });
     if (rc) return rc;
@@ -2754,7 +2753,7 @@ int daisy_item_apply_counts(float *Q, float *g, float *cnt, int64_t rows, int32_
     int rc = dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         hipLaunchKernelGGL((k_item_apply_counts<C>), dim3(grid_for(rows, C::GROUPS_PER_BLOCK * 2)), dim3(kBlock), 0,
-                           S(stream), Q, g, cnt, rows, (int)d, lr, reg_1, reg_2, stats);
+                           as_stream(stream), Q, g, cnt, rows, (int)d, lr, reg_1, reg_2, stats);
         return DAISY_OK;
     });
     if (rc) return rc;

@@ -34,7 +34,6 @@
 
 namespace daisy {
 
-static inline hipStream_t S(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---------------------------------------------------------------------------
 // epoch plan kernels
@@ -1027,31 +1026,12 @@ __global__ __launch_bounds__(kBlock) void k_user_edges(float *__restrict__ P, in
     }
 }
 
-// torch.optim.Adam single-tensor math (exp_avg.lerp_, addcmul_, addcdiv_), dense
-__global__ __launch_bounds__(kBlock) void k_adam_dense(float *__restrict__ W, float *__restrict__ g,
-                                                       float *__restrict__ m, float *__restrict__ v,
-                                                       int64_t n, float step_size, float beta1,
-                                                       float beta2, float eps, float bc2_sqrt) {
-    const float w1 = 1.f - beta1, w2 = 1.f - beta2;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-         e += (int64_t)gridDim.x * blockDim.x) {
-        const float gg = g[e];
-        const float mm = fmaf(w1, gg - m[e], m[e]);          // lerp(m, g, 1-beta1)
-        const float vv = fmaf(w2 * gg, gg, beta2 * v[e]);    // mul_(beta2).addcmul_(g,g,1-beta2)
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        W[e] = W[e] - step_size * (mm / denom);
-        m[e] = mm;
-        v[e] = vv;
-        g[e] = 0.f;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Dense Adam without touching every row in every step.  torch's Adam moves every element in every step (the moments
 // decay without a gradient), which at table sizes beyond the batch is most of the step's traffic.  But a row's
 // update sequence depends on nothing but its own gradients: a row without gradient in steps a+1..b can be brought
 // from its state after step a to its state after step b in registers (b - a zero-gradient updates, the very
-// expressions of k_adam_dense with g = 0) whenever it is next needed - before the step that reads it, or at a flush.
+// expressions of k_adam_dense, dense_opt.hip, with g = 0) whenever it is next needed - before the step that reads it, or at a flush.
 // last[r] = the step row r has been updated to.  table[s] = (lr / (1 - beta1^s), sqrt(1 - beta2^s)) as the dense
 // entry point computes them on the host, so the replay uses the same bits.  Result: identical to daisy_adam_dense
 // in every step (tested bit for bit), HBM traffic proportional to the rows a step touches.
@@ -1119,38 +1099,11 @@ __global__ __launch_bounds__(kBlock) void k_adam_flush(AdamTable T, int64_t rows
     }
 }
 
-// torch.optim.Adagrad single-tensor math (defaults): state_sum.addcmul_(g, g); w.addcdiv_(g, sqrt(state_sum) + eps, -lr)
-__global__ __launch_bounds__(kBlock) void k_adagrad_dense(float *__restrict__ W, float *__restrict__ g,
-                                                          float *__restrict__ ss, int64_t n, float lr, float eps) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const float gg = g[e];
-        const float s2 = fmaf(gg, gg, ss[e]);
-        W[e] = W[e] - lr * (gg / (sqrtf(s2) + eps));
-        ss[e] = s2;
-        g[e] = 0.f;
-    }
-}
-
-// torch.optim.RMSprop single-tensor math (defaults): sq.mul_(alpha).addcmul_(g, g, 1-alpha); w.addcdiv_(g, sqrt(sq) + eps, -lr)
-__global__ __launch_bounds__(kBlock) void k_rmsprop_dense(float *__restrict__ W, float *__restrict__ g,
-                                                          float *__restrict__ sq, int64_t n, float lr, float alpha,
-                                                          float eps) {
-    const float w2 = 1.f - alpha;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const float gg = g[e];
-        const float s2 = fmaf(w2 * gg, gg, alpha * sq[e]);
-        W[e] = W[e] - lr * (gg / (sqrtf(s2) + eps));
-        sq[e] = s2;
-        g[e] = 0.f;
-    }
-}
-
 // ---------------------------------------------------------------------------
 // plan construction (host side)
 // ---------------------------------------------------------------------------
 static int plan_alloc(daisy_epoch_plan **out, int64_t max_triples, int64_t U, int64_t I) {
-    daisy_epoch_plan *p = new daisy_epoch_plan();
-    memset(p, 0, sizeof(*p));          // no device memory yet: each layout allocates at its first build
+    daisy_epoch_plan *p = new daisy_epoch_plan();      // (all zero: no device memory yet, each layout allocates at its first build)
     p->max_triples = max_triples; p->U = U; p->I = I;
     *out = p;
     return DAISY_OK;
@@ -1158,7 +1111,7 @@ static int plan_alloc(daisy_epoch_plan **out, int64_t max_triples, int64_t U, in
 
 // buffers of the sorted layout (kind 0)
 static int plan_need_sorted(daisy_epoch_plan *p) {
-    if (p->arena) return DAISY_OK;
+    if (p->arena.bytes()) return DAISY_OK;
     const int64_t max_triples = p->max_triples;
     const size_t n2 = 2 * (size_t)max_triples;
     const size_t ta = sort_pairs_u32_u64_temp_bytes(n2), tb = sort_pairs_u64_u64_temp_bytes(n2);
@@ -1166,45 +1119,27 @@ static int plan_need_sorted(daisy_epoch_plan *p) {
     p->temp_bytes = ta > tb ? ta : tb;
     if (tc > p->temp_bytes) p->temp_bytes = tc;
     if (td > p->temp_bytes) p->temp_bytes = td;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    size_t o_k32[2], o_v64[2];
-    o_k32[0] = take(n2 * 4); o_k32[1] = take(n2 * 4);
-    o_v64[0] = take(n2 * 8); o_v64[1] = take(n2 * 8);
-    const size_t o_s32 = take((size_t)max_triples * 4);   // sorted sample keys survive the entry sort
-    const size_t o_sv = take((size_t)max_triples * 8);
-    const size_t o_ss = take(n2 * 4), o_sn = take(n2 * 4), o_so = take(((size_t)max_triples + 2) * 4);
-    const size_t o_rt = take(256);
-    const size_t o_tmp = take(p->temp_bytes);
-    p->arena_bytes = off;
-    hipError_t e = hipMalloc(&p->arena, p->arena_bytes);
-    if (e != hipSuccess) {
-        set_error("epoch_plan_build: hipMalloc(%zu) failed: %s", p->arena_bytes, hipGetErrorString(e));
-        p->arena = nullptr;
-        p->arena_bytes = 0;
-        return DAISY_ERR_HIP;
+    DeviceArena &a = p->arena;
+    a.add(&p->k32[0], n2 * 4); a.add(&p->k32[1], n2 * 4);
+    a.add(&p->v64[0], n2 * 8); a.add(&p->v64[1], n2 * 8);
+    a.add(&p->ukey, (size_t)max_triples * 4);   // sorted sample keys survive the entry sort
+    a.add(&p->uval, (size_t)max_triples * 8);
+    a.add(&p->run_key, n2 * 4); a.add(&p->run_cnt, n2 * 4); a.add(&p->run_off, ((size_t)max_triples + 2) * 4);
+    a.add(&p->run_total, 256);
+    a.add(&p->temp, p->temp_bytes);
+    if (int rc = a.alloc("epoch_plan_build")) {
+        a.release();
+        return rc;
     }
-    char *b = (char *)p->arena;
-    for (int k = 0; k < 2; ++k) {
-        p->k32[k] = (uint32_t *)(b + o_k32[k]);
-        p->v64[k] = (uint64_t *)(b + o_v64[k]);
-        p->k64[k] = nullptr;                        // allocated on demand (rare: > 32 key bits)
-    }
-    p->ukey = (uint32_t *)(b + o_s32);
-    p->uval = (uint64_t *)(b + o_sv);
-    p->run_key = (uint32_t *)(b + o_ss);
-    p->run_cnt = (uint32_t *)(b + o_sn);
-    p->run_off = (int32_t *)(b + o_so);
-    p->run_total = (uint32_t *)(b + o_rt);
-    p->bad = (int *)(b + o_rt + 64);
+    p->k64[0] = p->k64[1] = nullptr;                // allocated on demand (rare: > 32 key bits)
+    p->bad = (int *)((char *)p->run_total + 64);
     p->ekey = nullptr; p->eval = nullptr;
     p->umask = p->imask = 0;
-    p->temp = b + o_tmp;
     return DAISY_OK;
 }
 
 static int plan_free(daisy_epoch_plan *p) {
-    hipError_t e = p->arena ? hipFree(p->arena) : hipSuccess;
+    const hipError_t e = p->arena.release() ? hipSuccess : hipGetLastError();
     for (int k = 0; k < 2; ++k)
         if (p->k64[k]) (void)hipFree(p->k64[k]);
     if (p->parena) (void)hipFree(p->parena);
@@ -1446,7 +1381,7 @@ int daisy_epoch_plan_destroy(daisy_epoch_plan *plan) {
 }
 
 size_t daisy_epoch_plan_bytes(const daisy_epoch_plan *plan) {
-    return plan ? plan->arena_bytes + plan->parena_bytes : 0;
+    return plan ? plan->arena.bytes() + plan->parena_bytes : 0;
 }
 
 int64_t daisy_epoch_plan_num_batches(const daisy_epoch_plan *plan) {
@@ -1467,7 +1402,7 @@ int daisy_epoch_plan_build(daisy_epoch_plan *plan, const int32_t *triples, int64
     DAISY_CHECK_ARG(order_mode != DAISY_ORDER_PERM || perm != nullptr,
                     "epoch_plan_build: DAISY_ORDER_PERM needs perm");
     return plan_build(plan, triples, n_triples, 0, perm, order_mode, seed, epoch, batch_size, user_base,
-                      flags, S(stream));
+                      flags, as_stream(stream));
 }
 
 static int report_bad_ids(const int *bad_dev, const char *who, int64_t U, int64_t I, hipStream_t s) {
@@ -1488,14 +1423,14 @@ int daisy_epoch_plan_validate(const daisy_epoch_plan *plan, daisy_stream_t strea
     DAISY_CHECK_ARG(plan != nullptr, "epoch_plan_validate: NULL plan");
     if (!plan->built) { set_error("epoch_plan_validate: plan has not been built"); return DAISY_ERR_STATE; }
     if (plan->kind == 1) return DAISY_OK;            // a train index is validated when it is created
-    return report_bad_ids(plan->bad, "epoch_plan_build", plan->U, plan->I, S(stream));
+    return report_bad_ids(plan->bad, "epoch_plan_build", plan->U, plan->I, as_stream(stream));
 }
 
 int daisy_bpr_ctx_validate_batch(const daisy_bpr_ctx *ctx, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx != nullptr, "ctx_validate_batch: NULL context");
     if (!ctx->batch_set) { set_error("ctx_validate_batch: no batch set"); return DAISY_ERR_STATE; }
     if (!ctx->own_plan || !ctx->own_plan->built || ctx->v.ukey != ctx->own_plan->ukey) return DAISY_OK;   // from an epoch plan
-    return report_bad_ids(ctx->own_plan->bad, "set_batch", ctx->U, ctx->I, S(stream));
+    return report_bad_ids(ctx->own_plan->bad, "set_batch", ctx->U, ctx->I, as_stream(stream));
 }
 
 int daisy_epoch_plan_read_batch(const daisy_epoch_plan *plan, int64_t k, int32_t *u, int32_t *i,
@@ -1505,9 +1440,9 @@ int daisy_epoch_plan_read_batch(const daisy_epoch_plan *plan, int64_t k, int32_t
     if (!plan->built) { set_error("epoch_plan_read_batch: plan has not been built"); return DAISY_ERR_STATE; }
     DAISY_CHECK_ARG(k >= 0 && k < plan->num_batches, "epoch_plan_read_batch: batch %lld not in 0..%lld",
                     (long long)k, (long long)plan->num_batches);
-    if (plan->kind == 1) return plan_read_batch_partitioned(plan, k, u, i, j, ent_item, ent_s, ent_u, B_out_host, S(stream));
+    if (plan->kind == 1) return plan_read_batch_partitioned(plan, k, u, i, j, ent_item, ent_s, ent_u, B_out_host, as_stream(stream));
     const BatchView v = plan_view(plan, k);
-    hipLaunchKernelGGL(k_unpack_batch, dim3(grid_for(2 * v.B, kBlock)), dim3(kBlock), 0, S(stream), v, u, i,
+    hipLaunchKernelGGL(k_unpack_batch, dim3(grid_for(2 * v.B, kBlock)), dim3(kBlock), 0, as_stream(stream), v, u, i,
                        j, ent_item, ent_s, ent_u);
     DAISY_LAUNCH_CHECK();
     if (B_out_host) *B_out_host = v.B;
@@ -1518,7 +1453,7 @@ int daisy_feistel_positions(int64_t n, uint64_t seed, uint64_t epoch, int64_t *o
                             daisy_stream_t stream) {
     DAISY_CHECK_ARG(out && n > 0 && n <= ((int64_t)1 << 30), "feistel_positions: n must be in 1..2^30");
     FeistelKey fk = make_feistel_key((uint64_t)n, seed, epoch);
-    hipLaunchKernelGGL(k_feistel_perm, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, S(stream), n, fk, out);
+    hipLaunchKernelGGL(k_feistel_perm, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, as_stream(stream), n, fk, out);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }
@@ -1527,7 +1462,7 @@ int daisy_feistel_positions_at(const int64_t *ids, int64_t n_ids, int64_t n, uin
                                int64_t *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ids && out && n_ids > 0 && n > 0 && n <= ((int64_t)1 << 30), "feistel_positions_at: bad argument");
     FeistelKey fk = make_feistel_key((uint64_t)n, seed, epoch);
-    hipLaunchKernelGGL(k_feistel_at, dim3(grid_for(n_ids, kBlock)), dim3(kBlock), 0, S(stream), ids, n_ids, n, fk, out);
+    hipLaunchKernelGGL(k_feistel_at, dim3(grid_for(n_ids, kBlock)), dim3(kBlock), 0, as_stream(stream), ids, n_ids, n, fk, out);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }
@@ -1549,11 +1484,10 @@ int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int6
     c->cur_plan = c->pre_plan = nullptr; c->cur_k = c->pre_k = -1; c->cur_gen = c->pre_gen = 0;
     c->pre_P = nullptr; c->pre_stats = nullptr; c->pre_n = 0; c->pre_ready = false;
     c->p_stream_mode = -1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_coef = take((size_t)max_batch * 8);
-    const size_t o_part = take(((size_t)kMaxGrid * 8 + kPreBlocks) * 8);
-    const size_t o_tt = take((size_t)max_batch * 12);
+    DeviceArena &a = c->arena;
+    a.add(&c->coef, (size_t)max_batch * 8);
+    a.add(&c->partials, ((size_t)kMaxGrid * 8 + kPreBlocks) * 8);
+    a.add(&c->tmp_triples, (size_t)max_batch * 12);
     // edge records: two per chunk of the user pass (B samples) or of the item pass (2B entries)
     size_t max_chunks = 0;
     (void)dispatch_d(d, [&](auto cfg) {
@@ -1572,46 +1506,27 @@ int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int6
     });
     const size_t n_edge = 2 * max_chunks;
     c->edge_chunks = (int64_t)max_chunks;
-    const size_t o_ev = take(n_edge * (size_t)d * 4), o_eu = take(n_edge * 4), o_en = take(n_edge * 8);
-    const size_t o_ew = take(n_edge * 4);
-    const size_t o_ec = take(n_edge * 16);        // staged item pass: (n_pos, n_neg, coefficient sum, -) per edge record
+    a.add(&c->edge_vec, n_edge * (size_t)d * 4); a.add(&c->edge_user, n_edge * 4); a.add(&c->edge_n, n_edge * 8);
+    a.add(&c->edge_whole, n_edge * 4);
+    a.add(&c->edge_cnt, n_edge * 16);             // staged item pass: (n_pos, n_neg, coefficient sum, -) per edge record
     const size_t n_eb = max_chunks / kEdgeBlock + 2;      // block sums of long edge chains (k_staged_item_edge_blocks)
-    const size_t o_ebv = take(n_eb * (size_t)d * 4), o_ebi = take(n_eb * 4), o_ebc = take(n_eb * 16), o_ebt = take(n_eb * 4);
+    a.add(&c->eb_vec, n_eb * (size_t)d * 4); a.add(&c->eb_item, n_eb * 4); a.add(&c->eb_cnt, n_eb * 16); a.add(&c->eb_through, n_eb * 4);
     // the item pass's own edge records in the three-launch form (its chunks are at least 2 entries x 16 lane groups)
     const size_t merge_b = (size_t)(max_batch < kMergeMaxBatch ? max_batch : kMergeMaxBatch);
     const size_t chunks2 = 2 * merge_b / 32 + 2, n_edge2 = 2 * chunks2;
-    const size_t o_e2v = take(n_edge2 * (size_t)d * 4), o_e2i = take(n_edge2 * 4), o_e2c = take(n_edge2 * 16);
-    const size_t o_e2w = take(n_edge2 * 4);
-    const size_t o_sr = take((kMaxItemSlices + 1) * 8);
-    const size_t o_ps = take((size_t)max_batch * (size_t)d * 4);
-    const size_t o_pn = take((size_t)user_num * 4);
-    c->arena_bytes = off;
-    hipError_t e = hipMalloc(&c->arena, c->arena_bytes);
-    if (e != hipSuccess) {
-        set_error("ctx_create: hipMalloc(%zu) failed: %s", c->arena_bytes, hipGetErrorString(e));
+    a.add(&c->edge2_vec, n_edge2 * (size_t)d * 4); a.add(&c->edge2_item, n_edge2 * 4); a.add(&c->edge2_cnt, n_edge2 * 16);
+    a.add(&c->edge2_whole, n_edge2 * 4);
+    a.add(&c->slice_rng, (kMaxItemSlices + 1) * 8);
+    a.add(&c->p_stage, (size_t)max_batch * (size_t)d * 4);
+    a.add(&c->p_sqnorm, (size_t)user_num * 4);
+    if (int rc = a.alloc("ctx_create")) {
         delete c;
-        return DAISY_ERR_HIP;
+        return rc;
     }
-    char *base = (char *)c->arena;
-    c->coef = (float2 *)(base + o_coef);
-    c->partials = (double *)(base + o_part);
-    c->tmp_triples = (int32_t *)(base + o_tt);
-    c->edge_vec = (float *)(base + o_ev);
-    c->edge_user = (int32_t *)(base + o_eu);
-    c->edge_n = (float *)(base + o_en);
-    c->edge_whole = (int32_t *)(base + o_ew);
-    c->edge_cnt = (float *)(base + o_ec);
-    c->eb_vec = (float *)(base + o_ebv); c->eb_item = (int32_t *)(base + o_ebi);
-    c->eb_cnt = (float *)(base + o_ebc); c->eb_through = (int32_t *)(base + o_ebt);
     c->eb_blocks = (int64_t)n_eb;
-    c->edge2_vec = (float *)(base + o_e2v); c->edge2_item = (int32_t *)(base + o_e2i);
-    c->edge2_cnt = (float *)(base + o_e2c); c->edge2_whole = (int32_t *)(base + o_e2w);
     c->edge2_chunks = (int64_t)chunks2;
-    c->slice_rng = (int64_t *)(base + o_sr);
     c->n_slices = 0;
     c->batch_kind = 0;
-    c->p_stage = (float *)(base + o_ps);
-    c->p_sqnorm = (float *)(base + o_pn);
     c->p_sqnorm_of = nullptr;
     *out = c;
     return DAISY_OK;
@@ -1621,7 +1536,7 @@ int daisy_bpr_ctx_destroy(daisy_bpr_ctx *ctx) {
     if (!ctx) return DAISY_OK;
     int rc = DAISY_OK;
     if (ctx->own_plan) rc = plan_free(ctx->own_plan);
-    hipError_t e = hipFree(ctx->arena);
+    const hipError_t e = ctx->arena.release() ? hipSuccess : hipGetLastError();
     delete ctx;
     if (e != hipSuccess) {
         set_error("ctx_destroy: hipFree failed: %s", hipGetErrorString(e));
@@ -1632,7 +1547,7 @@ int daisy_bpr_ctx_destroy(daisy_bpr_ctx *ctx) {
 
 size_t daisy_bpr_ctx_scratch_bytes(const daisy_bpr_ctx *ctx) {
     if (!ctx) return 0;
-    return ctx->arena_bytes + (ctx->own_plan ? ctx->own_plan->arena_bytes : 0);
+    return ctx->arena.bytes() + (ctx->own_plan ? ctx->own_plan->arena.bytes() : 0);
 }
 
 static int ensure_own_plan(daisy_bpr_ctx *ctx) {
@@ -1706,7 +1621,7 @@ int daisy_bpr_set_batch_from_triples(daisy_bpr_ctx *ctx, const int32_t *triples,
     if (rc) return rc;
     // a one-batch plan over the selected rows
     rc = plan_build(ctx->own_plan, triples, B, idx ? 0 : start, idx, idx ? DAISY_ORDER_PERM : DAISY_ORDER_IDENTITY,
-                    0, 0, B, user_base, ctx->pointwise ? DAISY_PLAN_POINTWISE : 0, S(stream), idx ? n_triples : -1);
+                    0, 0, B, user_base, ctx->pointwise ? DAISY_PLAN_POINTWISE : 0, as_stream(stream), idx ? n_triples : -1);
     if (rc) return rc;
     ctx->v = plan_view(ctx->own_plan, 0);
     ctx->sv = stream_view_of(ctx->v);
@@ -1722,7 +1637,7 @@ int daisy_bpr_set_batch(daisy_bpr_ctx *ctx, const int32_t *u, const int32_t *i, 
     DAISY_CHECK_ARG(ctx && u && i && j, "set_batch: NULL argument");
     DAISY_CHECK_ARG(B > 0 && B <= ctx->max_batch, "set_batch: B=%lld not in 1..%lld", (long long)B,
                     (long long)ctx->max_batch);
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(k_pack_triples, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, s, u, i, j, B,
                        ctx->tmp_triples);
     DAISY_LAUNCH_CHECK();
@@ -1744,7 +1659,7 @@ static int forward_impl(daisy_bpr_ctx *ctx, const float *P, const float *Q, int3
     DAISY_CHECK_ARG((loss_type >= DAISY_LOSS_CL) == (ctx->v.pointwise != 0),
                     "forward: loss type %d does not match the batch layout (point-wise=%d)", loss_type,
                     ctx->v.pointwise);
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const BatchView &v = ctx->v;
     const int d = ctx->d;
     int grid = 0;
@@ -1780,7 +1695,7 @@ int daisy_bpr_forward(daisy_bpr_ctx *ctx, const float *P, const float *Q, int32_
 int daisy_bpr_finalize(daisy_bpr_ctx *ctx, double *stats, float reg_1, float reg_2,
                        double *epoch_acc, double *step_loss, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && stats, "finalize: NULL argument");
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1), 0, S(stream), stats, reg_1, reg_2, epoch_acc,
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1), 0, as_stream(stream), stats, reg_1, reg_2, epoch_acc,
                        step_loss);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -1795,7 +1710,7 @@ static int item_grad_impl(daisy_bpr_ctx *ctx, const float *P, const float *Q, co
                     "item_grad: bad item_mode %d", item_mode);
     ctx->last_item_mode = item_mode;
     if (!ctx->fwd_done) { set_error("item_grad: forward has not run for this batch"); return DAISY_ERR_STATE; }
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const BatchView &v = ctx->v;
     const int d = ctx->d;
     const bool reg = (reg_1 != 0.f) || (reg_2 != 0.f);
@@ -1878,7 +1793,7 @@ int daisy_bpr_item_grad_reg(daisy_bpr_ctx *ctx, const float *Q, const double *st
         using C = decltype(cfg);
         hipLaunchKernelGGL((k_item_reg<C>),
                            dim3(grid_for(2 * v.B < ctx->I ? 2 * v.B : ctx->I, C::GROUPS_PER_BLOCK * 2)),
-                           dim3(kBlock), 0, S(stream), Q, v, d, stats, reg_1, reg_2, gQ);
+                           dim3(kBlock), 0, as_stream(stream), Q, v, d, stats, reg_1, reg_2, gQ);
         return DAISY_OK;
     });
     if (rc) return rc;
@@ -1892,7 +1807,7 @@ static int user_pass(daisy_bpr_ctx *ctx, float *P, const float *Q, const double 
     ctx->p_sqnorm_of = nullptr;   // P rows change behind the row-norm cache of the staged step
     ctx->pre_ready = false;       // (and behind a pre-norm the staged step computed ahead)
     if (!ctx->fwd_done) { set_error("user update: forward has not run for this batch"); return DAISY_ERR_STATE; }
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const BatchView &v = ctx->v;
     const int d = ctx->d;
     static const int user_kernel = getenv("DAISY_USER_KERNEL") ? atoi(getenv("DAISY_USER_KERNEL")) : 1;
@@ -1949,7 +1864,7 @@ static int item_apply_impl(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, in
         set_error("item_sgd_apply: the current batch comes from a partitioned plan; only dense != 0 applies there");
         return DAISY_ERR_STATE;
     }
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const int d = ctx->d;
     const BatchView &v = ctx->v;
     const int64_t n = dense ? ctx->I : (2 * v.B < ctx->I ? 2 * v.B : ctx->I);   // upper bound of rows
@@ -1974,21 +1889,10 @@ int daisy_bpr_item_sgd_apply(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, 
     return item_apply_impl(ctx, Q, gQ, lr, dense, nullptr, 0.f, 0.f, false, stream);
 }
 
-int daisy_adam_dense(float *W, float *g, float *m, float *v, int64_t n, float lr, float beta1,
-                     float beta2, float eps, int64_t step, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(W && g && m && v && n > 0 && step >= 1, "adam_dense: bad argument");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(k_adam_dense, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, S(stream), W, g, m,
-                       v, n, (float)((double)lr / bc1), beta1, beta2, eps, (float)sqrt(bc2));
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
 int daisy_adam_lazy_table(float lr, float beta1, float beta2, int64_t n_steps, float *table_host) {
     DAISY_CHECK_ARG(table_host && n_steps >= 1, "adam_lazy_table: bad argument");
     table_host[0] = table_host[1] = 0.f;                              // step 0 does not exist
-    for (int64_t s = 1; s <= n_steps; ++s) {                          // the host arithmetic of daisy_adam_dense
+    for (int64_t s = 1; s <= n_steps; ++s) {                          // the host arithmetic of daisy_adam_dense (dense_opt.hip)
         const double bc1 = 1.0 - pow((double)beta1, (double)s), bc2 = 1.0 - pow((double)beta2, (double)s);
         table_host[2 * s] = (float)((double)lr / bc1);
         table_host[2 * s + 1] = (float)sqrt(bc2);
@@ -2027,7 +1931,7 @@ int daisy_adam_lazy_catchup(daisy_bpr_ctx *ctx, float *P, float *mP, float *vP, 
                             int64_t step, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && P && mP && vP && lastP && Q && mQ && vQ && lastQ && table && step >= 1, "adam_lazy_catchup: bad argument");
     return adam_lazy_batch(ctx, false, P, nullptr, mP, vP, lastP, Q, nullptr, mQ, vQ, lastQ, table, beta1, beta2, eps, step,
-                           S(stream));
+                           as_stream(stream));
 }
 
 int daisy_adam_lazy_step(daisy_bpr_ctx *ctx, float *P, float *gP, float *mP, float *vP, int32_t *lastP, float *Q,
@@ -2035,7 +1939,7 @@ int daisy_adam_lazy_step(daisy_bpr_ctx *ctx, float *P, float *gP, float *mP, flo
                          float eps, int64_t step, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && P && gP && mP && vP && lastP && Q && gQ && mQ && vQ && lastQ && table && step >= 1,
                     "adam_lazy_step: bad argument");
-    return adam_lazy_batch(ctx, true, P, gP, mP, vP, lastP, Q, gQ, mQ, vQ, lastQ, table, beta1, beta2, eps, step, S(stream));
+    return adam_lazy_batch(ctx, true, P, gP, mP, vP, lastP, Q, gQ, mQ, vQ, lastQ, table, beta1, beta2, eps, step, as_stream(stream));
 }
 
 int daisy_adam_lazy_flush(float *W, float *m, float *v, int32_t *last, int64_t rows, int32_t d, const float *table,
@@ -2045,28 +1949,11 @@ int daisy_adam_lazy_flush(float *W, float *m, float *v, int32_t *last, int64_t r
     const AdamHyper h{reinterpret_cast<const float2 *>(table), beta1, beta2, eps, (int32_t)step};
     int rc = dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
-        hipLaunchKernelGGL((k_adam_flush<C>), dim3(grid_for(rows, C::GROUPS_PER_BLOCK * 2)), dim3(kBlock), 0, S(stream), T,
+        hipLaunchKernelGGL((k_adam_flush<C>), dim3(grid_for(rows, C::GROUPS_PER_BLOCK * 2)), dim3(kBlock), 0, as_stream(stream), T,
                            rows, (int)d, h);
         return DAISY_OK;
     });
     if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_adagrad_dense(float *W, float *g, float *state_sum, int64_t n, float lr, float eps, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(W && g && state_sum && n > 0, "adagrad_dense: bad argument");
-    hipLaunchKernelGGL(k_adagrad_dense, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, S(stream), W, g, state_sum, n, lr,
-                       eps);
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_rmsprop_dense(float *W, float *g, float *square_avg, int64_t n, float lr, float alpha, float eps,
-                        daisy_stream_t stream) {
-    DAISY_CHECK_ARG(W && g && square_avg && n > 0, "rmsprop_dense: bad argument");
-    hipLaunchKernelGGL(k_rmsprop_dense, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, S(stream), W, g, square_avg, n,
-                       lr, alpha, eps);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }
@@ -2089,7 +1976,7 @@ int daisy_bpr_sgd_step(daisy_bpr_ctx *ctx, float *P, float *Q, int32_t loss_type
         // the staged step (bpr_staged.hip): pairwise losses without FM biases; anything else runs the phase kernels
         if (staged_supported(ctx, loss_type))
             return staged_sgd_step(ctx, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, epoch_acc, step_loss,
-                                   S(stream));
+                                   as_stream(stream));
         item_mode = DAISY_ITEM_CHUNKED;
     }
     DAISY_CHECK_ARG(gQ != nullptr, "sgd_step: gQ is NULL");
@@ -2117,7 +2004,7 @@ int daisy_bpr_fit_epoch_sgd(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, fl
     if ((item_mode == DAISY_ITEM_CHUNKED || item_mode == DAISY_ITEM_FUSED) && small_epoch_supported(ctx, plan, loss_type)) {
         DAISY_CHECK_ARG(plan->U == ctx->U && plan->I == ctx->I, "fit_epoch: plan does not fit the context");
         return small_fit_epoch(ctx, plan, P, Q, loss_type, gamma, lr, reg_1, reg_2, stats, epoch_acc, step_losses,
-                               S(stream));
+                               as_stream(stream));
     }
     for (int64_t k = 0; k < plan->num_batches; ++k) {
         int rc = daisy_bpr_set_batch_from_plan(ctx, plan, k, stream);

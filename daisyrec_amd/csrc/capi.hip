@@ -71,7 +71,7 @@ int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const in
                    float *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(table && idx && out && rows > 0 && n > 0 && what >= 0 && what <= 3,
                     "membench: bad argument");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     int rc = dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         hipLaunchKernelGGL((k_membench<C>), dim3(grid_for(n, C::GROUPS_PER_BLOCK * 4)), dim3(kBlock), 0,

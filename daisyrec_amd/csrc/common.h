@@ -5,11 +5,15 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "../../include/daisyrec_amd.h"
 
 namespace daisy {
 
 void set_error(const char *fmt, ...);
+
+inline hipStream_t as_stream(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 #define DAISY_CHECK_ARG(cond, ...)          \
     do {                                    \
@@ -442,10 +446,32 @@ inline FeistelKey make_feistel_key(uint64_t n, uint64_t seed, uint64_t epoch) {
     return fk;
 }
 
+// ---- the dropout and noise stream of every model
+// the library's counter hash: 32 random bits of element `idx` of stream `stream` under `seed`
+__host__ __device__ __forceinline__ uint32_t counter_hash(uint64_t seed, uint32_t stream, uint64_t idx) {
+    const uint32_t h = mix32((uint32_t)idx ^ (uint32_t)seed);
+    return mix32(h + (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32) + stream * 0x85EBCA6Bu);
+}
+
+// keep mask of element `idx` of dropout stream `stream` (one stream per MLP layer input)
+__host__ __device__ __forceinline__ bool drop_keep(uint64_t seed, uint32_t stream, uint64_t idx,
+                                                   uint32_t thresh) {
+    return counter_hash(seed, stream, idx) >= thresh;
+}
+
+// the threshold of drop_keep for dropout probability p (0: dropout off - every element kept)
+inline uint32_t keep_threshold(float p) {
+    if (!(p > 0.f)) return 0u;
+    const double t = (double)p * 4294967296.0;
+    return (t >= 4294967295.0) ? 4294967295u : (uint32_t)t;
+}
+
 // ----------------------------------------------------------------------------
 // rocPRIM wrappers live in sort.hip (keeps the heavy headers in one TU)
 // ----------------------------------------------------------------------------
 size_t sort_pairs_i32_temp_bytes(int64_t n);
+// scratch that serves every id sort of 1..n items: a smaller sort may ask for more than the largest one (sort.hip)
+size_t sort_pairs_i32_temp_bytes_upto(int64_t n);
 // stable LSD radix sort of (key,val) int32 pairs on bits [0,end_bit)
 int sort_pairs_i32(void *temp, size_t temp_bytes, const int32_t *kin, int32_t *kout,
                    const int32_t *vin, int32_t *vout, int64_t n, int end_bit, hipStream_t s);
@@ -493,6 +519,44 @@ inline int bits_for(int64_t n) {  // number of bits needed for values in [0, n)
 }
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// One device allocation cut into slots: add() records a slot at the next 256-byte boundary, in call order (slots added
+// one after the other are adjacent in memory); alloc() allocates and points every recorded pointer at its slot.
+struct DeviceArena {
+    template <class T>
+    void add(T **ptr, size_t bytes) {
+        slots_.push_back(Slot{reinterpret_cast<void **>(ptr), total_});
+        total_ += align_up(bytes);
+    }
+    int alloc(const char *what) {
+        const hipError_t e = hipMalloc(&base_, total_);
+        if (e != hipSuccess) {
+            base_ = nullptr;
+            set_error("%s: hipMalloc(%zu) failed: %s", what, total_, hipGetErrorString(e));
+            return DAISY_ERR_HIP;
+        }
+        for (const Slot &sl : slots_) *sl.ptr = static_cast<char *>(base_) + sl.off;
+        return DAISY_OK;
+    }
+    size_t bytes() const { return total_; }
+    bool release() {            // false: hipFree failed.  (Empty afterwards: it can be laid out again.)
+        const bool ok = !base_ || hipFree(base_) == hipSuccess;
+        *this = DeviceArena();
+        return ok;
+    }
+
+private:
+    struct Slot { void **ptr; size_t off; };
+    std::vector<Slot> slots_;
+    void *base_ = nullptr;
+    size_t total_ = 0;
+};
+
+// the dense optimiser of the library-issued epoch loops (dense_opt.hip).  optimizer: 0 sgd, 1 adam, 2 adagrad, 3 rmsprop,
+// with torch's default hyper-parameters; t: Adam's step count (>= 1)
+int dense_opt_check(const char *what, int32_t optimizer, const float *state0, const float *state1);
+int dense_opt_step(int32_t optimizer, float *W, float *g, float *state0, float *state1, int64_t n, float lr, int64_t t,
+                   daisy_stream_t stream);
 
 // ---------------------------------------------------------------------------
 // loss coefficient (daisy/utils/loss.py)

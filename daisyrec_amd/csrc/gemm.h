@@ -1,0 +1,56 @@
+// The MFMA products of the library (gemm.hip): C = A B^T-style contractions with arbitrary strides, in fp32, with bf16
+// MFMA inputs, or over operands stored as bf16.  Internal: the exported entry points are daisy_gemm_* (daisyrec_amd.h).
+#pragma once
+#include "common.h"
+
+namespace daisy {
+
+constexpr int kGemmBM = 128;   // block tile rows (2 x 2 waves, each 64 rows)
+
+enum { EPI_STORE = 0, EPI_BIAS_RELU = 1, EPI_GATE = 2, EPI_ATOMIC = 3 };
+
+struct GemmOp {
+    const float *A; int64_t sam, sak;     // A(m,k) = A[m*sam + k*sak]
+    const float *B; int64_t sbn, sbk;     // B(n,k) = B[n*sbn + k*sbk]
+    float *C; int64_t ldc, scn;           // C(m,n) = C[m*ldc + n*scn]   (scn = 0 means 1)
+    int64_t M; int N; int64_t K;
+    const float *bias;                    // EPI_BIAS_RELU
+    const float *gate; int64_t ldg;       // EPI_GATE: out = acc * (gate(m,n) > 0 ? gate_scale : 0)
+    float gate_scale;
+    uint32_t drop_thresh, drop_stream;    // dropout on output element (m,n), idx = m*N + n; thresh 0: off
+    float drop_scale;
+    uint64_t drop_seed;
+    int64_t k_chunk;                      // reduction range per blockIdx.z
+    int64_t slice_stride;                 // EPI_ATOMIC: != 0 - slice z STORES its partial product at C + z * slice_stride
+                                          // (summed in slice order by k_reduce_slices: reproducible); 0 - fp32 atomics into C
+    int vec_a, vec_b;                     // set by launch_gemm: operand qualifies for the float4 path
+    int bf16;                             // throughput mode: bf16-input MFMA where the tile shape allows it
+    // bf16 STORAGE (precision level 2: activations and a copy of the weights live as bf16 in HBM): when A16 is set the
+    // operands are read through A16 / B16 (same strides, in elements), the gate through G16, and the result goes to
+    // C16 (EPI_BIAS_RELU / EPI_GATE) or, in fp32, to C (EPI_ATOMIC)
+    const uint16_t *A16, *B16, *G16;
+    uint16_t *C16;
+};
+
+// The launchers exist for the epilogues their callers use (instantiated in gemm.hip; another one is a link error):
+//   launch_gemm       STORE, BIAS_RELU, GATE, ATOMIC: fp32 storage (op.bf16: bf16 MFMA inputs where the shape allows it)
+//   launch_gemm_h     BIAS_RELU, GATE, ATOMIC: bf16 storage, only for shapes gemm_h_ok accepts
+//   launch_gemm_pair  STORE, ATOMIC: two products of the same (N, tile width) in one launch
+template <int EPI> void launch_gemm(GemmOp op, hipStream_t s);
+template <int EPI> void launch_gemm_h(GemmOp op, hipStream_t s);
+template <int EPI> void launch_gemm_pair(GemmOp a, GemmOp b, hipStream_t s);
+
+// shapes the bf16-storage kernel takes: whole tiles, k ranges in multiples of 32, 16-byte aligned rows
+bool gemm_h_ok(const GemmOp &op);
+
+// fp32 -> bf16 (round to nearest even) of a [n / cols][cols] matrix, as stored (y) and transposed (yt)
+void to_bf16_and_transpose(const float *x, int64_t n, int cols, uint16_t *y, uint16_t *yt, hipStream_t s);
+
+// ---- the fp32 MFMA product (k_gemm): C(m,n) = sum_k A(m,k) B(n,k) with
+// A(m,k) = A[m*sam + k*sak], B(n,k) = B[n*sbn + k*sbk], C(m,n) = C[m*ldc + n].  k_chunk >= K: C is written;
+// k_chunk < K: slice z of the k range [z*k_chunk, (z+1)*k_chunk) STORES its partial product at C + z*slice_stride
+// (slice_stride != 0; the caller sums the slices in a fixed order).
+void gemm_f32(const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbn, int64_t sbk, float *C, int64_t ldc,
+              int64_t M, int N, int64_t K, int64_t k_chunk, int64_t slice_stride, hipStream_t s);
+
+}  // namespace daisy

@@ -6,7 +6,6 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "neumf_internal.h"
 
 namespace daisy {
 
@@ -259,13 +258,12 @@ using namespace daisy;
 
 struct daisy_lgcn_graph {
     int64_t U, I, nnz;
-    void *arena;
-    size_t arena_bytes;
+    DeviceArena arena;
     uint32_t *ekey;
     uint2 *esu;
     float2 *coef;
     int reproducible;     // daisy_lgcn_graph_set_reproducible
-    void *edge_arena;     // scratch of the segmented reduction (edge records), sized for edge_d
+    DeviceArena edge_arena;   // scratch of the segmented reduction (edge records), sized for edge_d
     int edge_d;
     float *edge_vec, *edge_b;
     int32_t *edge_item, *edge_whole;
@@ -294,22 +292,20 @@ __global__ void k_lg_row_ptr(const uint32_t *__restrict__ ekey, int64_t nnz, int
 
 // (re)allocate the edge-record scratch of the products for row width d
 static int ensure_edges(daisy_lgcn_graph *g, int d) {
-    if (g->edge_arena && g->edge_d == d) return DAISY_OK;
-    if (g->edge_arena) { (void)hipFree(g->edge_arena); g->edge_arena = nullptr; }
+    if (g->edge_arena.bytes() && g->edge_d == d) return DAISY_OK;
+    g->edge_arena.release();
     const size_t chunks = (size_t)segsum_chunks(g->nnz, d) + 2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_v = take(2 * chunks * (size_t)d * 4), o_i = take(2 * chunks * 4), o_b = take(2 * chunks * 4),
-                 o_w = take(chunks * 4);
-    DAISY_HIP(hipMalloc(&g->edge_arena, off));
-    char *base = (char *)g->edge_arena;
-    g->edge_vec = (float *)(base + o_v); g->edge_item = (int32_t *)(base + o_i);
-    g->edge_b = (float *)(base + o_b); g->edge_whole = (int32_t *)(base + o_w);
+    g->edge_arena.add(&g->edge_vec, 2 * chunks * (size_t)d * 4);
+    g->edge_arena.add(&g->edge_item, 2 * chunks * 4);
+    g->edge_arena.add(&g->edge_b, 2 * chunks * 4);
+    g->edge_arena.add(&g->edge_whole, chunks * 4);
+    if (int rc = g->edge_arena.alloc("lgcn: the edge records")) {
+        g->edge_arena.release();
+        return rc;
+    }
     g->edge_d = d;
     return DAISY_OK;
 }
-
-static inline hipStream_t LS(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 extern "C" {
 
@@ -320,24 +316,21 @@ int daisy_lgcn_graph_create(daisy_lgcn_graph **out, const int32_t *users, const 
     DAISY_CHECK_ARG(users && items && n > 0 && user_num > 0 && item_num > 0 &&
                         user_num + item_num < ((int64_t)1 << 31),
                     "lgcn_graph_create: bad argument");
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t N = user_num + item_num;
     // scratch: keys, sorted keys, unique pairs, swapped, swapped sorted, counts, runs, degrees, sort temp
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_k0 = take(n * 8), o_k1 = take(n * 8), o_un = take(n * 8), o_sw = take(n * 8), o_ss = take(n * 8);
-    const size_t o_cnt = take(n * 4), o_runs = take(16), o_deg = take((size_t)N * 4);
+    uint64_t *k0, *k1, *un, *sw, *ss;
+    uint32_t *cnt, *runs;
+    int32_t *deg;
+    void *tmp;
     size_t tb = sort_keys_u64_temp_bytes(n);
     if (rle_u64_temp_bytes(n) > tb) tb = rle_u64_temp_bytes(n);
-    const size_t o_tmp = take(tb);
-    char *scratch = nullptr;
-    DAISY_HIP(hipMalloc((void **)&scratch, off));
-    auto fail = [&](int rc) { (void)hipFree(scratch); return rc; };
-    uint64_t *k0 = (uint64_t *)(scratch + o_k0), *k1 = (uint64_t *)(scratch + o_k1), *un = (uint64_t *)(scratch + o_un);
-    uint64_t *sw = (uint64_t *)(scratch + o_sw), *ss = (uint64_t *)(scratch + o_ss);
-    uint32_t *cnt = (uint32_t *)(scratch + o_cnt), *runs = (uint32_t *)(scratch + o_runs);
-    int32_t *deg = (int32_t *)(scratch + o_deg);
-    void *tmp = scratch + o_tmp;
+    DeviceArena scratch;
+    scratch.add(&k0, n * 8); scratch.add(&k1, n * 8); scratch.add(&un, n * 8); scratch.add(&sw, n * 8); scratch.add(&ss, n * 8);
+    scratch.add(&cnt, n * 4); scratch.add(&runs, 16); scratch.add(&deg, (size_t)N * 4);
+    scratch.add(&tmp, tb);
+    if (int rc = scratch.alloc("lgcn_graph_create")) return rc;
+    auto fail = [&](int rc) { scratch.release(); return rc; };
     hipLaunchKernelGGL(k_lg_pair_keys, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, s, users, items, n, k0);
     int rc = sort_keys_u64(tmp, tb, k0, k1, n, 64, s);
     if (rc) return fail(rc);
@@ -352,44 +345,39 @@ int daisy_lgcn_graph_create(daisy_lgcn_graph **out, const int32_t *users, const 
     daisy_lgcn_graph *g = new daisy_lgcn_graph();
     g->U = user_num; g->I = item_num; g->nnz = 2 * m;
     g->reproducible = 0;
-    g->edge_arena = nullptr; g->edge_d = 0;
+    g->edge_d = 0;
     g->row_ptr_host = nullptr;
     g->row_ptr_dev = nullptr;
     g->mirror = nullptr;
     g->segs = nullptr; g->long_rows = nullptr; g->seg_part = nullptr;
     g->nsegs = g->nlong = g->nslots = 0;
-    size_t goff = 0;
-    auto gtake = [&](size_t bytes) { size_t o = goff; goff += align_up(bytes); return o; };
-    const size_t g_k = gtake((size_t)g->nnz * 4), g_s = gtake((size_t)g->nnz * 8), g_c = gtake((size_t)g->nnz * 8);
-    g->arena_bytes = goff;
-    if (hipMalloc(&g->arena, goff) != hipSuccess) {
-        set_error("lgcn_graph_create: hipMalloc(%zu) failed", goff);
+    g->arena.add(&g->ekey, (size_t)g->nnz * 4);
+    g->arena.add(&g->esu, (size_t)g->nnz * 8);
+    g->arena.add(&g->coef, (size_t)g->nnz * 8);
+    if (int arc = g->arena.alloc("lgcn_graph_create")) {
         delete g;
-        return fail(DAISY_ERR_HIP);
+        return fail(arc);
     }
-    g->ekey = (uint32_t *)((char *)g->arena + g_k);
-    g->esu = (uint2 *)((char *)g->arena + g_s);
-    g->coef = (float2 *)((char *)g->arena + g_c);
     (void)hipMemsetAsync(deg, 0, (size_t)N * 4, s);
     hipLaunchKernelGGL(k_lg_degrees, dim3(grid_for(m, kBlock * 4)), dim3(kBlock), 0, s, un, m, user_num, deg, sw);
     rc = sort_keys_u64(tmp, tb, sw, ss, m, 64, s);
-    if (rc) { (void)hipFree(g->arena); delete g; return fail(rc); }
+    if (rc) { g->arena.release(); delete g; return fail(rc); }
     hipLaunchKernelGGL(k_lg_entries, dim3(grid_for(2 * m, kBlock * 4)), dim3(kBlock), 0, s, un, ss, m, user_num, deg,
                        g->ekey, g->esu, g->coef);
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         set_error("lgcn_graph_create: kernel failure");
-        (void)hipFree(g->arena); delete g;
+        g->arena.release(); delete g;
         return fail(DAISY_ERR_HIP);
     }
-    (void)hipFree(scratch);
+    scratch.release();
     *out = g;
     return DAISY_OK;
 }
 
 int daisy_lgcn_graph_destroy(daisy_lgcn_graph *g) {
     if (!g) return DAISY_OK;
-    if (g->arena) (void)hipFree(g->arena);
-    if (g->edge_arena) (void)hipFree(g->edge_arena);
+    g->arena.release();
+    g->edge_arena.release();
     if (g->row_ptr_host) free(g->row_ptr_host);
     if (g->row_ptr_dev) (void)hipFree(g->row_ptr_dev);
     if (g->mirror) (void)hipFree(g->mirror);
@@ -407,12 +395,12 @@ int daisy_lgcn_graph_set_reproducible(daisy_lgcn_graph *g, int32_t flag) {
 }
 
 int64_t daisy_lgcn_graph_nnz(const daisy_lgcn_graph *g) { return g ? g->nnz : 0; }
-size_t daisy_lgcn_graph_bytes(const daisy_lgcn_graph *g) { return g ? g->arena_bytes : 0; }
+size_t daisy_lgcn_graph_bytes(const daisy_lgcn_graph *g) { return g ? g->arena.bytes() : 0; }
 
 int daisy_lgcn_graph_read(const daisy_lgcn_graph *g, int32_t *row, int32_t *col, float *val,
                           daisy_stream_t stream) {
     DAISY_CHECK_ARG(g && row && col && val, "lgcn_graph_read: NULL argument");
-    hipLaunchKernelGGL(k_lg_read, dim3(grid_for(g->nnz, kBlock * 4)), dim3(kBlock), 0, LS(stream), g->ekey, g->esu,
+    hipLaunchKernelGGL(k_lg_read, dim3(grid_for(g->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), g->ekey, g->esu,
                        g->coef, g->nnz, row, col, val);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -420,7 +408,7 @@ int daisy_lgcn_graph_read(const daisy_lgcn_graph *g, int32_t *row, int32_t *col,
 
 int daisy_lgcn_spmm(const daisy_lgcn_graph *g, const float *X, float *Y, int32_t d, daisy_stream_t stream) {
     DAISY_CHECK_ARG(g && X && Y && X != Y && d > 0, "lgcn_spmm: bad argument");
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     DAISY_HIP(hipMemsetAsync(Y, 0, (size_t)(g->U + g->I) * d * 4, s));
     if (g->reproducible) {
         if (g->nnz > 0)
@@ -442,7 +430,7 @@ int daisy_lgcn_spmm_rows(const daisy_lgcn_graph *g, const float *X, float *Yrows
     const int64_t N = g->U + g->I;
     DAISY_CHECK_ARG(row_lo >= 0 && row_lo <= row_hi && row_hi <= N, "lgcn_spmm_rows: rows %lld..%lld outside 0..%lld",
                     (long long)row_lo, (long long)row_hi, (long long)N);
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     daisy_lgcn_graph *gm = const_cast<daisy_lgcn_graph *>(g);      // caches and scratch only: the matrix is untouched
     if (!gm->row_ptr_host) {          // once: the first entry of every row (one host sync)
         int64_t *dev = nullptr;
@@ -494,7 +482,7 @@ int daisy_lgcn_spmm_ex(const daisy_lgcn_graph *g, const float *X, int64_t ldx, f
     DAISY_CHECK_ARG(d >= 1 && d <= kMaxD && ldx >= d && ldy >= d, "lgcn_spmm_ex: d=%d ldx=%lld ldy=%lld out of range",
                     (int)d, (long long)ldx, (long long)ldy);
     DAISY_CHECK_ARG(node_p >= 0.f && node_p < 1.f, "lgcn_spmm_ex: node_p=%g outside [0, 1)", (double)node_p);
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t N = g->U + g->I;
     daisy_lgcn_graph *gm = const_cast<daisy_lgcn_graph *>(g);      // caches only: the matrix is untouched
     if (!gm->segs) {                  // once: row offsets and the row segments (one host synchronisation)
@@ -574,7 +562,7 @@ int daisy_lgcn_spmm_ex(const daisy_lgcn_graph *g, const float *X, int64_t ldx, f
 int daisy_lgcn_propagate(const daisy_lgcn_graph *g, const float *E0, int32_t d, int32_t num_layers,
                          float *work, float *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(g && E0 && work && out && d > 0 && num_layers >= 0, "lgcn_propagate: bad argument");
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t nel = (g->U + g->I) * (int64_t)d;
     const int grid = grid_for(nel, kBlock * 4);
     DAISY_HIP(hipMemcpyAsync(out, E0, (size_t)nel * 4, hipMemcpyDeviceToDevice, s));
@@ -595,7 +583,7 @@ int daisy_lgcn_propagate(const daisy_lgcn_graph *g, const float *E0, int32_t d, 
 int daisy_lgcn_backprop(const daisy_lgcn_graph *g, const float *G, int32_t d, int32_t num_layers, float *work,
                         float *dE0, daisy_stream_t stream) {
     DAISY_CHECK_ARG(g && G && work && dE0 && d > 0 && num_layers >= 0, "lgcn_backprop: bad argument");
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t nel = (g->U + g->I) * (int64_t)d;
     const int grid = grid_for(nel, kBlock * 4);
     const float *t = G;                               // Horner: T <- G + A T, L times
@@ -613,7 +601,7 @@ int daisy_lgcn_backprop(const daisy_lgcn_graph *g, const float *G, int32_t d, in
 
 int daisy_axpby_f32(float *x, float a, float b, float *y, int64_t n, int32_t zero_x, daisy_stream_t stream) {
     DAISY_CHECK_ARG(x && y && n > 0, "axpby_f32: bad argument");
-    hipLaunchKernelGGL(k_axpby_zero, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, LS(stream), x, a, b, y, n,
+    hipLaunchKernelGGL(k_axpby_zero, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), x, a, b, y, n,
                        (int)zero_x);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -622,7 +610,7 @@ int daisy_axpby_f32(float *x, float a, float b, float *y, int64_t n, int32_t zer
 int daisy_csr_row_sum(const int64_t *indptr, const int32_t *cols, const float *X, int64_t rows, int32_t d,
                       float *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(indptr && cols && X && out && rows > 0 && d > 0, "csr_row_sum: bad argument");
-    hipLaunchKernelGGL(k_csr_row_sum, dim3(grid_for(rows, kBlock / 16)), dim3(kBlock), 0, LS(stream), indptr, cols, X,
+    hipLaunchKernelGGL(k_csr_row_sum, dim3(grid_for(rows, kBlock / 16)), dim3(kBlock), 0, as_stream(stream), indptr, cols, X,
                        rows, (int)d, out);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -634,7 +622,7 @@ int daisy_lgcn_reg_grad(const float *E0, const int32_t *u, const int32_t *i, con
     DAISY_CHECK_ARG(E0 && u && i && j && stats && dE0 && count_ws && B > 0 && d > 0 && user_num > 0 && item_num > 0,
                     "lgcn_reg_grad: bad argument");
     if (reg_1 == 0.f && reg_2 == 0.f) return DAISY_OK;
-    hipStream_t s = LS(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t N = user_num + item_num;
     hipLaunchKernelGGL(k_lg_reg_count, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, s, u, i, j, B, user_num,
                        (int)pointwise, count_ws);

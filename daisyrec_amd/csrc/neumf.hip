@@ -2,725 +2,27 @@
 //
 //   forward   k_nmf_gather      x0 = [uM[u] | iM[item]] (dropout of layer 1 applied), g = uG[u]*iG[item],
 //                               regulariser sums of the gathered rows (training only)
-//             k_gemm<EPI_BIAS_RELU>   x_l = ReLU(x_{l-1} W_l^T + b_l) (* dropout mask of layer l+1):
-//                               fp32 MFMA 32x32x2 tiles, LDS-staged, register-prefetched
+//             launch_gemm<EPI_BIAS_RELU>   x_l = ReLU(x_{l-1} W_l^T + b_l) (* dropout mask of layer l+1): the MFMA
+//                               products of gemm.hip
 //             k_nmf_predict     pred = <Wp, [g | x_L]> + bp
 //   loss      k_nmf_loss        criterion epilogue shared with MF (pair_coef) -> d loss / d pred
 //             k_nmf_finalize    norms + NeuMF.calc_loss value
 //   backward  k_nmf_pred_bwd    dZ_L = dpred * Wp[mlp part] gated by x_L > 0;  gWp, gbp
-//             k_gemm<EPI_ATOMIC>      gW_l += dZ_l^T x_{l-1}   (reduction over the batch rows, split over blocks)
+//             launch_gemm<EPI_ATOMIC>   gW_l += dZ_l^T x_{l-1}   (reduction over the batch rows, split over blocks)
 //             k_colsum          gb_l += column sums of dZ_l
-//             k_gemm<EPI_GATE>  dZ_{l-1} = (dZ_l W_l) gated by x_{l-1} > 0 (layer 1: dropout mask of x0)
+//             launch_gemm<EPI_GATE>     dZ_{l-1} = (dZ_l W_l) gated by x_{l-1} > 0 (layer 1: dropout mask of x0)
 //             k_nmf_scatter     embedding gradients (fp32 atomics into the dense gradient tables) +
 //                               the regulariser gradients exactly as NeuMFRecommender.py:149-167 lists them
 // Dropout: x_{l-1} is stored already masked and scaled, so "x > 0" carries mask and ReLU gate at once.
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm.h"
+#include "mfma.h"
 #include "neumf_internal.h"
-
-#include <type_traits>
-
-#ifndef DAISY_BKH
-#define DAISY_BKH 32        // k depth of the bf16-storage GEMM's tiles (32 or 64; -DDAISY_BKH=64 to try the other)
-#endif
+#include "pairs.h"
 
 namespace daisy {
-
-
-constexpr int kBK = 16;        // k depth of an LDS tile
-constexpr int kGemmBM = 128;   // block tile rows (2 x 2 waves, each 64 rows)
-constexpr int kLdsPad = 4;
-
-enum { EPI_STORE = 0, EPI_BIAS_RELU = 1, EPI_GATE = 2, EPI_ATOMIC = 3 };
-
-struct GemmOp {
-    const float *A; int64_t sam, sak;     // A(m,k) = A[m*sam + k*sak]
-    const float *B; int64_t sbn, sbk;     // B(n,k) = B[n*sbn + k*sbk]
-    float *C; int64_t ldc, scn;           // C(m,n) = C[m*ldc + n*scn]   (scn = 0 means 1)
-    int64_t M; int N; int64_t K;
-    const float *bias;                    // EPI_BIAS_RELU
-    const float *gate; int64_t ldg;       // EPI_GATE: out = acc * (gate(m,n) > 0 ? gate_scale : 0)
-    float gate_scale;
-    uint32_t drop_thresh, drop_stream;    // dropout on output element (m,n), idx = m*N + n; thresh 0: off
-    float drop_scale;
-    uint64_t drop_seed;
-    int64_t k_chunk;                      // reduction range per blockIdx.z
-    int64_t slice_stride;                 // EPI_ATOMIC: != 0 - slice z STORES its partial product at C + z * slice_stride
-                                          // (summed in slice order by k_reduce_slices: reproducible); 0 - fp32 atomics into C
-    int vec_a, vec_b;                     // set by launch_gemm: operand qualifies for the float4 path
-    int bf16;                             // throughput mode: bf16-input MFMA where the tile shape allows it
-    // bf16 STORAGE (precision level 2: activations and a copy of the weights live as bf16 in HBM): when A16 is set the
-    // operands are read through A16 / B16 (same strides, in elements), the gate through G16, and the result goes to
-    // C16 (EPI_BIAS_RELU / EPI_GATE) or, in fp32, to C (EPI_ATOMIC)
-    const uint16_t *A16, *B16, *G16;
-    uint16_t *C16;
-};
-
-template <int WN, int EPI, bool FAST, bool DROP>
-__device__ __forceinline__ void gemm_epilogue(const GemmOp &op, floatx16 (&acc)[2][WN], int64_t m0, int n0, int wm,
-                                              int wn, int lane, unsigned zslice) {
-    // lane holds column (lane % 32), rows (i/4)*8 + (lane/32)*4 + i%4 of each 32x32 block (all MFMA
-    // 32x32 shapes share this C/D map on gfx950).  epilogue: lane holds column (lane % 32), rows (i/4)*8 + (lane/32)*4 + i%4 of each 32x32 block.
-    // 32-bit offsets from the tile origin (a tile spans < 2^31 elements of C: 128 rows x ldc)
-    const int scn = op.scn ? (int)op.scn : 1;
-    float *__restrict__ Ct = op.C + m0 * op.ldc + (int64_t)n0 * scn;
-    // (the k slice this workgroup computed - k_gemm_h remaps workgroups to tiles, so that is NOT blockIdx.z there: until round 6
-    // the slices of the bf16-storage weight gradients landed in the slot of blockIdx.z, two workgroups per slot whenever the
-    // slice count was a multiple of 8 and an output had fewer than 8 tiles - partial products lost, unseen by tests that
-    // allowed 25 %; found by the bf16 oracle at 2 %)
-    if constexpr (EPI == EPI_ATOMIC) Ct += (int64_t)zslice * op.slice_stride;
-    const float *__restrict__ Gt = (EPI == EPI_GATE && op.gate) ? op.gate + m0 * op.ldg + n0 : nullptr;
-    const int ldc = (int)op.ldc, ldg = (int)op.ldg;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < WN; ++ni) {
-            const int nl = wn * 32 * WN + ni * 32 + lane % 32;
-            float bias = 0.f;
-            if constexpr (EPI == EPI_BIAS_RELU) bias = (FAST || n0 + nl < op.N) ? op.bias[n0 + nl] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int ml = wm * 64 + mi * 32 + (i / 4) * 8 + (lane / 32) * 4 + (i % 4);
-                if (!FAST && (m0 + ml >= op.M || n0 + nl >= op.N)) continue;
-                float v = acc[mi][ni][i];
-                if constexpr (EPI == EPI_BIAS_RELU) v = fmaxf(v + bias, 0.f);
-                if constexpr (EPI == EPI_GATE)
-                    if (Gt) v = (Gt[ml * ldg + nl] > 0.f) ? v * op.gate_scale : 0.f;
-                if constexpr (DROP)
-                    if (op.drop_thresh)
-                        v = drop_keep(op.drop_seed, op.drop_stream,
-                                      (uint64_t)(m0 + ml) * (uint64_t)op.N + (uint64_t)(n0 + nl), op.drop_thresh)
-                                ? v * op.drop_scale : 0.f;
-                if constexpr (EPI == EPI_ATOMIC) {
-                    if (op.slice_stride) Ct[ml * ldc + nl * scn] = v;
-                    else unsafeAtomicAdd(Ct + ml * ldc + nl * scn, v);
-                } else Ct[ml * ldc + nl * scn] = v;
-            }
-        }
-}
-
-// C = A * B^T-style contraction over k with arbitrary strides.  WN: 32-column MFMA blocks per wave
-// (block tile = 128 x 64*WN).  Operand tiles go global -> registers -> LDS (k-major, so the MFMA
-// fragment reads are conflict free; two LDS stages, one barrier per k tile) with the next tile's
-// loads in flight during the MFMAs.  Interior tiles of 16-byte aligned operands take a branch-free
-// float4 path (a guarded load costs a branch and a vmcnt drain each); edge tiles, k tails and
-// unaligned operands take the guarded scalar path.
-// FAST: every tile is interior, both operands qualify for the float4 path and the k range is a multiple
-// of kBK (checked by launch_gemm) - the guarded loader and its address registers are compiled out, which
-// is what lets four waves per SIMD share the MFMA pipe.
-template <int WN, int EPI, bool FAST, bool DROP>
-__device__ __forceinline__ void gemm_f32_tile(const GemmOp &op, unsigned bx, unsigned by, unsigned bz) {
-    constexpr int BM = kGemmBM, BN = 64 * WN;
-    constexpr int EA = BM * kBK / kBlock, EB = BN * kBK / kBlock;     // elements per thread per tile
-    constexpr int LA = BM + kLdsPad, LB = BN + kLdsPad;
-    __shared__ __attribute__((aligned(16))) float As[2][kBK * LA];
-    __shared__ __attribute__((aligned(16))) float Bs[2][kBK * LB];
-    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
-    const int wm = wave / 2, wn = wave % 2;
-    const int64_t m0 = (int64_t)bx * BM;
-    const int n0 = by * BN;
-    const int64_t k_lo = (int64_t)bz * op.k_chunk;
-    const int64_t k_hi = (k_lo + op.k_chunk < op.K) ? (k_lo + op.k_chunk) : op.K;
-    const bool a_kfast = (op.sak == 1), b_kfast = (op.sbk == 1);
-    const bool a_vec = FAST || (op.vec_a && (m0 + BM <= op.M)), b_vec = FAST || (op.vec_b && (n0 + BN <= op.N));
-
-    floatx16 acc[2][WN];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < WN; ++ni)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mi][ni][i] = 0.f;
-
-    float ra[EA], rb[EB];
-    // one operand tile [rows x kBK] -> registers.  vec: float4 along the contiguous dimension
-    auto load_op = [&](const float *__restrict__ P, int64_t srow, int64_t sk, bool kfast, bool vec, int64_t row0,
-                       int64_t nrows_total, int64_t kt, auto &r, auto rows_c, auto elems_c) {
-        constexpr int ROWS = decltype(rows_c)::value, E = decltype(elems_c)::value;
-        if (FAST || (vec && kt + kBK <= k_hi)) {
-            if (kfast) {                                   // 4 lanes cover the 16 k of one row
-                const float *src = P + (row0 + tid / 4) * srow + kt + (tid % 4) * 4;
-#pragma unroll
-                for (int q = 0; q < E / 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)q * (kBlock / 4) * srow);
-                    r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
-                }
-            } else {                                       // ROWS/4 lanes cover one k
-                const float *src = P + row0 + (tid % (ROWS / 4)) * 4 + (kt + tid / (ROWS / 4)) * sk;
-#pragma unroll
-                for (int q = 0; q < E / 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)q * (kBlock / (ROWS / 4)) * sk);
-                    r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
-                }
-            }
-        } else if constexpr (!FAST) {
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                const int e = tid + q * kBlock;
-                const int kk = kfast ? (e % kBK) : (e / ROWS);
-                const int rr = kfast ? (e / kBK) : (e % ROWS);
-                const int64_t row = row0 + rr, k = kt + kk;
-                r[q] = (row < nrows_total && k < k_hi) ? P[row * srow + k * sk] : 0.f;
-            }
-        }
-    };
-    auto store_op = [&](float *__restrict__ S, int ld, bool kfast, bool vec, bool full, auto &r, auto rows_c,
-                        auto elems_c) {
-        constexpr int ROWS = decltype(rows_c)::value, E = decltype(elems_c)::value;
-        if (FAST || (vec && full)) {
-            if (kfast) {
-#pragma unroll
-                for (int q = 0; q < E / 4; ++q) {
-                    const int row = tid / 4 + q * (kBlock / 4), k = (tid % 4) * 4;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) S[(k + t) * ld + row] = r[4 * q + t];
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < E / 4; ++q) {
-                    const int row = (tid % (ROWS / 4)) * 4, k = tid / (ROWS / 4) + q * (kBlock / (ROWS / 4));
-                    *reinterpret_cast<float4 *>(S + k * ld + row) = make_float4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
-                }
-            }
-        } else if constexpr (!FAST) {
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                const int e = tid + q * kBlock;
-                const int kk = kfast ? (e % kBK) : (e / ROWS);
-                const int rr = kfast ? (e / kBK) : (e % ROWS);
-                S[kk * ld + rr] = r[q];
-            }
-        }
-    };
-    using RA = std::integral_constant<int, BM>; using RB = std::integral_constant<int, BN>;
-    using NA = std::integral_constant<int, EA>; using NB = std::integral_constant<int, EB>;
-
-    if (k_lo < k_hi) {
-        load_op(op.A, op.sam, op.sak, a_kfast, a_vec, m0, op.M, k_lo, ra, RA{}, NA{});
-        load_op(op.B, op.sbn, op.sbk, b_kfast, b_vec, (int64_t)n0, (int64_t)op.N, k_lo, rb, RB{}, NB{});
-        store_op(As[0], LA, a_kfast, a_vec, k_lo + kBK <= k_hi, ra, RA{}, NA{});
-        store_op(Bs[0], LB, b_kfast, b_vec, k_lo + kBK <= k_hi, rb, RB{}, NB{});
-        __syncthreads();
-        int cur = 0;
-        for (int64_t kt = k_lo; kt < k_hi; kt += kBK) {
-            const bool more = kt + kBK < k_hi;
-            if (more) {
-                load_op(op.A, op.sam, op.sak, a_kfast, a_vec, m0, op.M, kt + kBK, ra, RA{}, NA{});
-                load_op(op.B, op.sbn, op.sbk, b_kfast, b_vec, (int64_t)n0, (int64_t)op.N, kt + kBK, rb, RB{}, NB{});
-            }
-            const float *as = As[cur] + (lane / 32) * LA + wm * 64 + lane % 32;
-            const float *bs = Bs[cur] + (lane / 32) * LB + wn * 32 * WN + lane % 32;
-            float a[2][2], b[2][WN];          // fragments of k-step s live in slot s&1: the next step's LDS
-#pragma unroll                                // reads are issued before this step's MFMAs
-            for (int mi = 0; mi < 2; ++mi) a[0][mi] = as[mi * 32];
-#pragma unroll
-            for (int ni = 0; ni < WN; ++ni) b[0][ni] = bs[ni * 32];
-#pragma unroll
-            for (int ks = 0; ks < kBK / 2; ++ks) {
-                const int c = ks & 1, nx = c ^ 1;
-                if (ks + 1 < kBK / 2) {
-#pragma unroll
-                    for (int mi = 0; mi < 2; ++mi) a[nx][mi] = as[(2 * ks + 2) * LA + mi * 32];
-#pragma unroll
-                    for (int ni = 0; ni < WN; ++ni) b[nx][ni] = bs[(2 * ks + 2) * LB + ni * 32];
-                }
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < WN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][mi], b[c][ni], acc[mi][ni], 0, 0, 0);
-            }
-            if (more) {                                    // the other stage: nobody reads it now
-                const bool full = kt + 2 * kBK <= k_hi;
-                store_op(As[cur ^ 1], LA, a_kfast, a_vec, full, ra, RA{}, NA{});
-                store_op(Bs[cur ^ 1], LB, b_kfast, b_vec, full, rb, RB{}, NB{});
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
-
-    gemm_epilogue<WN, EPI, FAST, DROP>(op, acc, m0, n0, wm, wn, lane, bz);
-}
-
-template <int WN, int EPI, bool FAST, bool DROP>
-__global__ __launch_bounds__(kBlock) void k_gemm(GemmOp op) {
-    gemm_f32_tile<WN, EPI, FAST, DROP>(op, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-// Two independent products in ONE launch (round 6): the user side's and the item side's table products of a NeuMF step are
-// each ~100 workgroups of 16 dependent k steps - latency-bound, 29-34 us per launch whatever the loader.  Side by side
-// (workgroups [0, ax) take `a`, the rest `b`; k slices beyond a product's own count leave at once) the pair costs what one did.
-template <int WN, int EPI>
-__global__ __launch_bounds__(kBlock) void k_gemm_pair(GemmOp a, GemmOp b, unsigned ax, unsigned az, unsigned bz_n) {
-    if (blockIdx.x < ax) { if (blockIdx.z < az) gemm_f32_tile<WN, EPI, false, false>(a, blockIdx.x, blockIdx.y, blockIdx.z); }
-    else if (blockIdx.z < bz_n) gemm_f32_tile<WN, EPI, false, false>(b, blockIdx.x - ax, blockIdx.y, blockIdx.z);
-}
-
-// ---------------------------------------------------------------------------------------------
-// bf16-input variant (throughput mode; BASELINE configs[3] names it): operands stay fp32 in HBM, are
-// rounded to bf16 (nearest-even) on their way into LDS and multiplied by v_mfma_f32_32x32x16_bf16
-// (fp32 accumulate, 16x the fp32 MFMA rate).  LDS tiles are row-major with k contiguous - a lane's
-// fragment is 8 consecutive k = one 16-byte read - at an 80-byte row pitch (odd multiple of 16 B:
-// conflict free).  Interior, aligned tiles only (launch_gemm falls back to the fp32 kernel otherwise).
-// ---------------------------------------------------------------------------------------------
-constexpr int kBK16 = 32, kLdk16 = kBK16 + 8;
-
-
-template <int WN, int EPI, bool DROP>
-__global__ __launch_bounds__(kBlock) void k_gemm_bf16(GemmOp op) {
-    constexpr int BM = kGemmBM, BN = 64 * WN;
-    constexpr int QA = BM * kBK16 / kBlock / 4, QB = BN * kBK16 / kBlock / 4;      // float4 loads per thread per tile
-    __shared__ __attribute__((aligned(16))) uint16_t As[2][BM * kLdk16];
-    __shared__ __attribute__((aligned(16))) uint16_t Bs[2][BN * kLdk16];
-    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
-    const int wm = wave / 2, wn = wave % 2;
-    const int64_t m0 = (int64_t)blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
-    const int64_t k_lo = (int64_t)blockIdx.z * op.k_chunk;
-    const int64_t k_hi = (k_lo + op.k_chunk < op.K) ? (k_lo + op.k_chunk) : op.K;
-    const bool a_kfast = (op.sak == 1), b_kfast = (op.sbk == 1);
-
-    floatx16 acc[2][WN];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < WN; ++ni)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mi][ni][i] = 0.f;
-
-    float ra[4 * QA], rb[4 * QB];
-    // k-contiguous operand: float4 along k (8 lanes cover the 32 k of a row).  Operand contiguous along
-    // its rows (the weight-gradient GEMM's two operands, W in the d-input GEMM): a thread takes ONE row
-    // and 4*Q consecutive k with scalar loads - each wave instruction still reads 64 consecutive rows of
-    // one k, 256 contiguous bytes - so that its bf16 pack is k-contiguous and lands in LDS as 16-byte
-    // writes (a float4 along the rows would have to be scattered with 2-byte stores).
-    auto load_op = [&](const float *__restrict__ P, int64_t srow, int64_t sk, bool kfast, int64_t row0, int64_t kt,
-                       auto &r, auto rows_c, auto q_c) {
-        constexpr int ROWS = decltype(rows_c)::value, Q = decltype(q_c)::value;
-        if (kfast) {
-            const float *src = P + (row0 + tid / 8) * srow + kt + (tid % 8) * 4;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)q * (kBlock / 8) * srow);
-                r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
-            }
-        } else {
-            const float *src = P + row0 + (tid % ROWS) + (kt + (int64_t)(tid / ROWS) * (4 * Q)) * sk;
-#pragma unroll
-            for (int q = 0; q < 4 * Q; ++q) r[q] = src[(int64_t)q * sk];
-        }
-    };
-    auto pack2 = [](float lo, float hi) { return bf16_pack2(lo, hi); };
-    auto store_op = [&](uint16_t *__restrict__ S, bool kfast, auto &r, auto rows_c, auto q_c) {
-        constexpr int ROWS = decltype(rows_c)::value, Q = decltype(q_c)::value;
-        if (kfast) {
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const int row = tid / 8 + q * (kBlock / 8), k = (tid % 8) * 4;
-                *reinterpret_cast<uint2 *>(S + row * kLdk16 + k) =
-                    make_uint2(pack2(r[4 * q], r[4 * q + 1]), pack2(r[4 * q + 2], r[4 * q + 3]));
-            }
-        } else {
-            uint16_t *dst = S + (tid % ROWS) * kLdk16 + (tid / ROWS) * (4 * Q);
-#pragma unroll
-            for (int q = 0; q < Q / 2; ++q)
-                *reinterpret_cast<uint4 *>(dst + 8 * q) =
-                    make_uint4(pack2(r[8 * q], r[8 * q + 1]), pack2(r[8 * q + 2], r[8 * q + 3]),
-                               pack2(r[8 * q + 4], r[8 * q + 5]), pack2(r[8 * q + 6], r[8 * q + 7]));
-        }
-    };
-    using RA = std::integral_constant<int, BM>; using RB = std::integral_constant<int, BN>;
-    using NA = std::integral_constant<int, QA>; using NB = std::integral_constant<int, QB>;
-
-    if (k_lo < k_hi) {
-        load_op(op.A, op.sam, op.sak, a_kfast, m0, k_lo, ra, RA{}, NA{});
-        load_op(op.B, op.sbn, op.sbk, b_kfast, (int64_t)n0, k_lo, rb, RB{}, NB{});
-        store_op(As[0], a_kfast, ra, RA{}, NA{});
-        store_op(Bs[0], b_kfast, rb, RB{}, NB{});
-        __syncthreads();
-        int cur = 0;
-        for (int64_t kt = k_lo; kt < k_hi; kt += kBK16) {
-            const bool more = kt + kBK16 < k_hi;
-            if (more) {
-                load_op(op.A, op.sam, op.sak, a_kfast, m0, kt + kBK16, ra, RA{}, NA{});
-                load_op(op.B, op.sbn, op.sbk, b_kfast, (int64_t)n0, kt + kBK16, rb, RB{}, NB{});
-            }
-            const uint16_t *as = As[cur] + (wm * 64 + lane % 32) * kLdk16 + (lane / 32) * 8;
-            const uint16_t *bs = Bs[cur] + (wn * 32 * WN + lane % 32) * kLdk16 + (lane / 32) * 8;
-#pragma unroll
-            for (int ks = 0; ks < kBK16 / 16; ++ks) {
-                bf16x8 a[2], b[WN];
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-                    a[mi] = *reinterpret_cast<const bf16x8 *>(as + mi * 32 * kLdk16 + ks * 16);
-#pragma unroll
-                for (int ni = 0; ni < WN; ++ni)
-                    b[ni] = *reinterpret_cast<const bf16x8 *>(bs + ni * 32 * kLdk16 + ks * 16);
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < WN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-            }
-            if (more) {
-                store_op(As[cur ^ 1], a_kfast, ra, RA{}, NA{});
-                store_op(Bs[cur ^ 1], b_kfast, rb, RB{}, NB{});
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
-    gemm_epilogue<WN, EPI, true, DROP>(op, acc, m0, n0, wm, wn, lane, blockIdx.z);
-}
-
-// bf16-STORAGE variant (precision level 2): both operands are bf16 in HBM, so a tile row of 32 k is 64 bytes -
-// 4 lanes x 16 bytes, copied to LDS as they are (no conversion, half the operand bytes of the fp32-storage
-// kernels above, which is what bounded them).  Operands that are contiguous along their rows instead of k (the
-// weight-gradient GEMM) keep that layout in LDS and are transposed by the fragment read (lds_frag_tr below).
-// Epilogues: bias + ReLU (+dropout) or gate with bf16 output (round to nearest even), or fp32 atomics (split-K).
-
-// Which tile a workgroup computes.  Workgroups go to the 8 XCDs round-robin by their linear id (observed, used for
-// speed only), and each XCD has its own L2: tiles that read the same operand panel are given to workgroups that
-// land on ONE XCD next to each other in time, so the panel comes from HBM once and from that L2 afterwards.
-//   one k range (forward, input gradient): the column tiles of one 128-row panel of A share it;
-//   split-K (weight gradient): all tiles of one k chunk share the chunk's two panels.
-struct TileId { unsigned x, y, z; };
-__device__ __forceinline__ TileId tile_of_block() {
-    const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
-    TileId t{blockIdx.x, blockIdx.y, blockIdx.z};
-    const unsigned lin = t.x + gx * (t.y + gy * t.z), xcd = lin % 8, slot = lin / 8;
-    if (gz > 1) {
-        if (gz % 8 == 0) {
-            const unsigned per = gx * gy, r = slot % per;
-            t.z = (slot / per) * 8 + xcd; t.x = r % gx; t.y = r / gx;
-        }
-    } else if (gx % 8 == 0) {
-        t.y = slot % gy; t.x = (slot / gy) * 8 + xcd;
-    }
-    return t;
-}
-
-constexpr int kBKH = DAISY_BKH, kLdkH = kBKH;          // k depth of a tile (64: 587 vs 610 TFLOP/s on the forward shape, step equal -
-                                                // 64 KB of LDS per workgroup halve the resident workgroups).  k-contiguous tiles
-                                                // are unpadded (64-byte rows); the four 16-byte chunks of row r sit at
-                                                // position chunk ^ ((r / 4) % 4): the fragment reads (ds_read_b128: 16 rows
-                                                // per LDS cycle) and the tile writes (two rows per 8-lane group) are then
-                                                // both conflict-free; the first version's 80-byte pitch left 31 % of the LDS
-                                                // cycles in bank conflicts (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE)
-// (32-deep tiles: 4 chunks per 64-byte row, chunk ^ ((r / 4) % 4); 64-deep: 8 chunks per 128-byte row, chunk ^ ((r / 2) % 8))
-__device__ __forceinline__ int swz_of_row(int row) { return kBKH == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7); }
-__device__ __forceinline__ int swz_chunk(int row, int chunk) { return chunk ^ swz_of_row(row); }
-// An operand that is contiguous along its ROWS instead of k (both operands of the weight-gradient GEMM: dZ^T and
-// X^T with k = the batch row) is copied to LDS as it lies in memory - [k][row] tiles, 16-byte loads along the rows -
-// and the MFMA fragment (8 consecutive k of one row per lane) comes out of gfx950's transposing LDS read:
-// ds_read_b64_tr_b16 hands lane i of a 16-lane group column i of the [4 k][16 rows] block whose 16 four-element
-// pieces the lanes address (measured: result[i][j] = piece[4j + i/4][i%4]), two of them per fragment.  The first
-// version read such operands with 2-byte global loads and packed them in registers: 265 TFLOP/s on the weight
-// gradients against 430-600 on the k-contiguous GEMMs.  Pitch rows + 32 halfwords: the 8 k rows one instruction
-// touches fall on 4 distinct 16-bank offsets, twice - the two LDS cycles its 512 bytes need anyway.
-constexpr int kPadT = 32;
-
-template <int WN, int EPI, bool DROP, bool AK, bool BK>      // AK / BK: operand A / B is contiguous along k (else along its rows)
-__global__ __launch_bounds__(kBlock) void k_gemm_h(GemmOp op) {
-    constexpr int BM = kGemmBM, BN = 64 * WN;
-    constexpr int LPT = kBKH / 8;                               // k-contiguous: lanes per tile row (16 bytes each)
-    constexpr int RPP = kBlock / LPT;                           //               tile rows per pass of the workgroup
-    constexpr int PTA = BM + kPadT, PTB = BN + kPadT;           // row-contiguous: halfwords per k row of the LDS tile
-    constexpr int kTileA = AK ? BM * kLdkH : kBKH * PTA, kTileB = BK ? BN * kLdkH : kBKH * PTB;
-    // one LDS block: two stages of the A and B tiles; the output tile of the bf16 epilogues reuses it afterwards
-    constexpr int kStage = 2 * (kTileA + kTileB), kOut = BM * (BN + 8);
-    __shared__ __attribute__((aligned(16))) uint16_t smem[kStage > kOut ? kStage : kOut];
-    uint16_t *const As0 = smem, *const Bs0 = smem + 2 * kTileA;
-    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
-    const int wm = wave / 2, wn = wave % 2;
-    const TileId tile = tile_of_block();
-    const int64_t m0 = (int64_t)tile.x * BM;
-    const int n0 = tile.y * BN;
-    const int64_t k_lo = (int64_t)tile.z * op.k_chunk;
-    const int64_t k_hi = (k_lo + op.k_chunk < op.K) ? (k_lo + op.k_chunk) : op.K;
-
-    floatx16 acc[2][WN];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < WN; ++ni)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mi][ni][i] = 0.f;
-
-    // registers of one tile: 16 bytes per load in both layouts (BM*32*2 / 256 threads = 2 loads for 128 rows)
-    // (clang's own vector type: arrays of HIP's uint4 class are not split into registers and went through scratch)
-    constexpr int NQ = BM * kBKH / 8 / kBlock;
-    u32x4 ra[NQ], rb[NQ];
-    auto load_op = [&](const uint16_t *__restrict__ P, int64_t srow, int64_t sk, auto kfast_c, int64_t row0, int64_t kt,
-                       auto &r, auto rows_c) {
-        constexpr int ROWS = decltype(rows_c)::value;
-        if constexpr (decltype(kfast_c)::value) {
-            const uint16_t *src = P + (row0 + tid / LPT) * srow + kt + (tid % LPT) * 8;
-#pragma unroll
-            for (int q = 0; q < ROWS / RPP; ++q) r[q] = *reinterpret_cast<const u32x4 *>(src + (int64_t)q * RPP * srow);
-        } else {
-            constexpr int VPR = ROWS / 8, KPP = kBlock / VPR;      // 16-byte vectors per k row; k rows per pass
-            const uint16_t *src = P + row0 + (tid % VPR) * 8 + (kt + tid / VPR) * sk;
-#pragma unroll
-            for (int q = 0; q < kBKH / KPP; ++q) r[q] = *reinterpret_cast<const u32x4 *>(src + (int64_t)q * KPP * sk);
-        }
-    };
-    auto store_op = [&](uint16_t *__restrict__ S, auto kfast_c, const auto &r, auto rows_c) {
-        constexpr int ROWS = decltype(rows_c)::value;
-        if constexpr (decltype(kfast_c)::value) {
-#pragma unroll
-            for (int q = 0; q < ROWS / RPP; ++q) {
-                const int row = tid / LPT + q * RPP;
-                *reinterpret_cast<u32x4 *>(S + row * kLdkH + swz_chunk(row, tid % LPT) * 8) = r[q];
-            }
-        } else {
-            constexpr int VPR = ROWS / 8, KPP = kBlock / VPR, PT = ROWS + kPadT;
-#pragma unroll
-            for (int q = 0; q < kBKH / KPP; ++q)
-                *reinterpret_cast<u32x4 *>(S + (tid / VPR + q * KPP) * PT + (tid % VPR) * 8) = r[q];
-        }
-    };
-    using RA = std::integral_constant<int, BM>; using RB = std::integral_constant<int, BN>;
-    using KA = std::integral_constant<bool, AK>; using KB = std::integral_constant<bool, BK>;
-    static_assert(BN <= BM, "tile registers are sized by the A tile");
-
-    if (k_lo < k_hi) {
-        load_op(op.A16, op.sam, op.sak, KA{}, m0, k_lo, ra, RA{});
-        load_op(op.B16, op.sbn, op.sbk, KB{}, (int64_t)n0, k_lo, rb, RB{});
-        store_op(As0, KA{}, ra, RA{});
-        store_op(Bs0, KB{}, rb, RB{});
-        __syncthreads();
-        int cur = 0;
-        for (int64_t kt = k_lo; kt < k_hi; kt += kBKH) {
-            const bool more = kt + kBKH < k_hi;
-            if (more) {
-                load_op(op.A16, op.sam, op.sak, KA{}, m0, kt + kBKH, ra, RA{});
-                load_op(op.B16, op.sbn, op.sbk, KB{}, (int64_t)n0, kt + kBKH, rb, RB{});
-            }
-            const uint16_t *At = As0 + cur * kTileA, *Bt = Bs0 + cur * kTileB;
-            // k-contiguous tile: lane -> row lane%32, k half lane/32.  [k][row] tile: the address of this lane's piece
-            // of the transposing read (k row 8*(lane/32) + (lane%16)/4, rows 16*((lane%32)/16) + 4*(lane%4) ...)
-            // (the row offsets wm*64 + mi*32 and wn*32*WN + ni*32 are multiples of 32: the swizzle of a lane's row
-            // depends on lane % 32 only)
-            const int sw = swz_of_row(lane % 32), half = lane / 32;
-            const uint16_t *as = AK ? At + (wm * 64 + lane % 32) * kLdkH
-                                    : At + (8 * (lane / 32) + (lane % 16) / 4) * PTA + wm * 64 + 16 * ((lane % 32) / 16) + 4 * (lane % 4);
-            const uint16_t *bs = BK ? Bt + (wn * 32 * WN + lane % 32) * kLdkH
-                                    : Bt + (8 * (lane / 32) + (lane % 16) / 4) * PTB + wn * 32 * WN + 16 * ((lane % 32) / 16) + 4 * (lane % 4);
-#pragma unroll
-            for (int ks = 0; ks < kBKH / 16; ++ks) {
-                bf16x8 a[2], b[WN];
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) {
-                    if constexpr (AK) a[mi] = *reinterpret_cast<const bf16x8 *>(as + mi * 32 * kLdkH + ((2 * ks + half) ^ sw) * 8);
-                    else a[mi] = lds_frag_tr(as + ks * 16 * PTA + mi * 32, PTA);
-                }
-#pragma unroll
-                for (int ni = 0; ni < WN; ++ni) {
-                    if constexpr (BK) b[ni] = *reinterpret_cast<const bf16x8 *>(bs + ni * 32 * kLdkH + ((2 * ks + half) ^ sw) * 8);
-                    else b[ni] = lds_frag_tr(bs + ks * 16 * PTB + ni * 32, PTB);
-                }
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < WN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-            }
-            if (more) {
-                store_op(As0 + (cur ^ 1) * kTileA, KA{}, ra, RA{});
-                store_op(Bs0 + (cur ^ 1) * kTileB, KB{}, rb, RB{});
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
-    if (EPI == EPI_ATOMIC || op.C16 == nullptr) {      // fp32 result: split-K atomics, or the tower's input gradient
-        gemm_epilogue<WN, EPI, true, DROP>(op, acc, m0, n0, wm, wn, lane, tile.z);
-    } else {        // bf16 output (interior tiles only: launch_gemm_h checks)
-        // The MFMA result layout gives a lane ONE column and 32 scattered rows: written directly that is 64 two-byte
-        // stores per lane.  So the tile takes a detour through LDS (the operand stages are dead by now) and
-        // leaves as 16-byte stores along its rows.
-        constexpr int LDT = BN + 8;                                       // halfwords per staged row (16-byte multiple)
-        uint16_t *Ts = smem;              // (the last k iteration ended with a barrier: every fragment read is done)
-        const uint16_t *__restrict__ Gt = (EPI == EPI_GATE && op.G16) ? op.G16 + m0 * op.ldg + n0 : nullptr;
-        const int ldg = (int)op.ldg;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < WN; ++ni) {
-                const int nl = wn * 32 * WN + ni * 32 + lane % 32;
-                float bias = 0.f;
-                if constexpr (EPI == EPI_BIAS_RELU) bias = op.bias[n0 + nl];
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {                       // rows ml, ml + 1 of column nl: one packed conversion
-                    const int ml = wm * 64 + mi * 32 + (i / 4) * 8 + (lane / 32) * 4 + (i % 4);
-                    float v[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        v[h] = acc[mi][ni][i + h];
-                        if constexpr (EPI == EPI_BIAS_RELU) v[h] = fmaxf(v[h] + bias, 0.f);
-                        if constexpr (DROP)
-                            if (op.drop_thresh)
-                                v[h] = drop_keep(op.drop_seed, op.drop_stream,
-                                                 (uint64_t)(m0 + ml + h) * (uint64_t)op.N + (uint64_t)(n0 + nl), op.drop_thresh)
-                                           ? v[h] * op.drop_scale : 0.f;
-                    }
-                    const uint32_t pk = bf16_pack2(v[0], v[1]);
-                    Ts[ml * LDT + nl] = (uint16_t)pk;
-                    Ts[(ml + 1) * LDT + nl] = (uint16_t)(pk >> 16);
-                }
-            }
-        __syncthreads();
-        constexpr int VPR = BN / 8;                                       // 16-byte vectors per tile row
-        uint16_t *__restrict__ Ct = op.C16 + m0 * op.ldc + n0;
-        for (int e = tid; e < BM * VPR; e += kBlock) {
-            const int row = e / VPR, c8 = (e % VPR) * 8;
-            uint4 v = *reinterpret_cast<const uint4 *>(Ts + row * LDT + c8);
-            if constexpr (EPI == EPI_GATE) {
-                if (Gt) {                                                 // gate: x > 0 of the layer input, 8 columns at a time
-                    const uint4 gq = *reinterpret_cast<const uint4 *>(Gt + (int64_t)row * ldg + c8);
-                    const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w};
-                    uint32_t vw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const uint16_t g0 = (uint16_t)gw[q], g1 = (uint16_t)(gw[q] >> 16);
-                        float lo = bf16_positive(g0) ? bf16_to_f32((uint16_t)vw[q]) * op.gate_scale : 0.f;
-                        float hi = bf16_positive(g1) ? bf16_to_f32((uint16_t)(vw[q] >> 16)) * op.gate_scale : 0.f;
-                        vw[q] = bf16_pack2(lo, hi);
-                    }
-                    v = make_uint4(vw[0], vw[1], vw[2], vw[3]);
-                }
-            }
-            *reinterpret_cast<uint4 *>(Ct + (int64_t)row * op.ldc + c8) = v;
-        }
-    }
-}
-
-// shapes the bf16-storage kernel takes: whole tiles, k ranges in multiples of 32, 16-byte aligned rows
-static bool gemm_h_ok(const GemmOp &op) {
-    const int bn = (op.N > 64) ? 128 : 64;
-    const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-    auto al = [](const uint16_t *p, int64_t srow, int64_t sk) {
-        if (((uintptr_t)p & 15) != 0) return false;
-        return sk == 1 ? (srow % 8 == 0) : (srow == 1 && sk % 8 == 0);     // 16-byte loads along k / along the rows
-    };
-    if (op.sak != 1 && op.sbk == 1) return false;          // (A along rows, B along k) is not a layout of the tower
-    return op.M % kGemmBM == 0 && op.N % bn == 0 && op.K % kBKH == 0 && (splits == 1 || op.k_chunk % kBKH == 0) &&
-           al(op.A16, op.sam, op.sak) && al(op.B16, op.sbn, op.sbk);
-}
-
-template <int EPI>
-static void launch_gemm_h(GemmOp op, hipStream_t s) {
-    const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-    if (op.k_chunk >= op.K) op.k_chunk = op.K;
-    const int bn = (op.N > 64) ? 128 : 64;
-    dim3 grid((unsigned)(op.M / kGemmBM), (unsigned)(op.N / bn), (unsigned)splits);
-    constexpr bool can_drop = (EPI == EPI_BIAS_RELU || EPI == EPI_GATE);
-    const bool drop = can_drop && op.drop_thresh != 0;
-    const bool ak = op.sak == 1, bk = op.sbk == 1;
-    auto go = [&](auto wn_c, auto drop_c, auto ak_c, auto bk_c) {
-        hipLaunchKernelGGL((k_gemm_h<decltype(wn_c)::value, EPI, decltype(drop_c)::value, decltype(ak_c)::value,
-                                     decltype(bk_c)::value>), grid, dim3(kBlock), 0, s, op);
-    };
-    using T = std::true_type; using F = std::false_type;
-    using W1 = std::integral_constant<int, 1>; using W2 = std::integral_constant<int, 2>;
-    auto go2 = [&](auto wn_c, auto drop_c) {          // the three operand layouts the tower uses
-        if (ak && bk) go(wn_c, drop_c, T{}, T{});         // forward:          X (k) x W (k)
-        else if (ak) go(wn_c, drop_c, T{}, F{});          // input gradient:   dZ (k) x W^T (rows)
-        else go(wn_c, drop_c, F{}, F{});                  // weight gradient:  dZ^T (rows) x X^T (rows)
-    };
-    if (op.N > 64) {
-        if constexpr (can_drop) { if (drop) go2(W2{}, T{}); else go2(W2{}, F{}); } else go2(W2{}, F{});
-    } else {
-        if constexpr (can_drop) { if (drop) go2(W1{}, T{}); else go2(W1{}, F{}); } else go2(W1{}, F{});
-    }
-}
-
-// fp32 -> bf16 (round to nearest even): the per-step copy of the MLP weights, [rows][cols] as stored and (yt)
-// transposed, so that the forward GEMM and the input-gradient GEMM both read W along their k
-__global__ void k_to_bf16(const float *__restrict__ x, int64_t n, int cols, uint16_t *__restrict__ y,
-                          uint16_t *__restrict__ yt) {
-    const int64_t rows = n / cols;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const uint16_t h = (uint16_t)bf16_rne(x[e]);
-        y[e] = h;
-        yt[(e % cols) * rows + e / cols] = h;
-    }
-}
-// float4 path preconditions: unit stride along one dimension, the other stride and the base 16-byte aligned
-static bool vec_ok(const float *p, int64_t s_row, int64_t s_k, int64_t k_chunk) {
-    if (((uintptr_t)p & 15) != 0) return false;
-    if (s_k == 1) return s_row % 4 == 0 && k_chunk % 4 == 0;
-    if (s_row == 1) return s_k % 4 == 0;
-    return false;
-}
-
-template <int EPI>
-static void launch_gemm(GemmOp op, hipStream_t s) {
-    const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-    if (op.k_chunk >= op.K) op.k_chunk = op.K;
-    op.vec_a = vec_ok(op.A, op.sam, op.sak, splits > 1 ? op.k_chunk : 4);
-    op.vec_b = vec_ok(op.B, op.sbn, op.sbk, splits > 1 ? op.k_chunk : 4);
-    const int bn = (op.N > 64) ? 128 : 64;
-    const bool fast = op.vec_a && op.vec_b && op.M % kGemmBM == 0 && op.N % bn == 0 && op.K % kBK == 0 &&
-                      (splits == 1 || op.k_chunk % kBK == 0);
-    dim3 grid((unsigned)((op.M + kGemmBM - 1) / kGemmBM), (unsigned)((op.N + bn - 1) / bn), (unsigned)splits);
-    const bool bf16 = op.bf16 && fast && op.K % kBK16 == 0 && (splits == 1 || op.k_chunk % kBK16 == 0);
-    auto go = [&](auto wn_c, auto fast_c, auto drop_c) {
-        if (bf16)
-            hipLaunchKernelGGL((k_gemm_bf16<decltype(wn_c)::value, EPI, decltype(drop_c)::value>), grid, dim3(kBlock), 0,
-                               s, op);
-        else
-            hipLaunchKernelGGL((k_gemm<decltype(wn_c)::value, EPI, decltype(fast_c)::value, decltype(drop_c)::value>),
-                               grid, dim3(kBlock), 0, s, op);
-    };
-    using T = std::true_type; using F = std::false_type;
-    using W1 = std::integral_constant<int, 1>; using W2 = std::integral_constant<int, 2>;
-    constexpr bool can_drop = (EPI == EPI_BIAS_RELU || EPI == EPI_GATE);
-    const bool drop = can_drop && op.drop_thresh != 0;
-    if (op.N > 64) {
-        if (fast) { if constexpr (can_drop) { if (drop) go(W2{}, T{}, T{}); else go(W2{}, T{}, F{}); } else go(W2{}, T{}, F{}); }
-        else      { if constexpr (can_drop) { if (drop) go(W2{}, F{}, T{}); else go(W2{}, F{}, F{}); } else go(W2{}, F{}, F{}); }
-    } else {
-        if (fast) { if constexpr (can_drop) { if (drop) go(W1{}, T{}, T{}); else go(W1{}, T{}, F{}); } else go(W1{}, T{}, F{}); }
-        else      { if constexpr (can_drop) { if (drop) go(W1{}, F{}, T{}); else go(W1{}, F{}, F{}); } else go(W1{}, F{}, F{}); }
-    }
-}
-
-// the fp32 product of neumf_internal.h (csrc/vae.hip's layers): k_gemm with plain stores, or its split-k slices stored apart
-void gemm_f32(const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbn, int64_t sbk, float *C, int64_t ldc,
-              int64_t M, int N, int64_t K, int64_t k_chunk, int64_t slice_stride, hipStream_t s) {
-    GemmOp op{};
-    op.A = A; op.sam = sam; op.sak = sak;
-    op.B = B; op.sbn = sbn; op.sbk = sbk;
-    op.C = C; op.ldc = ldc; op.M = M; op.N = N; op.K = K; op.k_chunk = k_chunk;
-    if (k_chunk < K) {
-        op.slice_stride = slice_stride;
-        launch_gemm<EPI_ATOMIC>(op, s);
-    } else {
-        launch_gemm<EPI_STORE>(op, s);
-    }
-}
-
-
-// two products of the same (N, tile width) in one launch (k_gemm_pair): guarded-loader kernels, fp32
-template <int EPI>
-static void launch_gemm_pair(GemmOp a, GemmOp b, hipStream_t s) {
-    auto prep = [](GemmOp &op) -> unsigned {
-        const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-        if (op.k_chunk >= op.K) op.k_chunk = op.K;
-        op.vec_a = vec_ok(op.A, op.sam, op.sak, splits > 1 ? op.k_chunk : 4);
-        op.vec_b = vec_ok(op.B, op.sbn, op.sbk, splits > 1 ? op.k_chunk : 4);
-        return (unsigned)splits;
-    };
-    const unsigned az = prep(a), bz = prep(b);
-    const int bn = (a.N > 64) ? 128 : 64;
-    const unsigned ax = (unsigned)((a.M + kGemmBM - 1) / kGemmBM), bx = (unsigned)((b.M + kGemmBM - 1) / kGemmBM);
-    const dim3 grid(ax + bx, (unsigned)((a.N + bn - 1) / bn), az > bz ? az : bz);
-    if (a.N > 64) hipLaunchKernelGGL((k_gemm_pair<2, EPI>), grid, dim3(kBlock), 0, s, a, b, ax, az, bz);
-    else hipLaunchKernelGGL((k_gemm_pair<1, EPI>), grid, dim3(kBlock), 0, s, a, b, ax, az, bz);
-}
 
 // ---------------------------------------------------------------------------------------------
 // the three pair layouts of daisy_neumf_scores plus the training batch
@@ -1866,14 +1168,6 @@ static void launch_table_commit(float *g, float *sum, const float *w, int64_t ro
                            ka, cb, kb, scale_b, stats, reg_1, reg_2, clear_counts, colscale);
 }
 
-__global__ __launch_bounds__(kBlock) void k_sgd_dense(float *__restrict__ W, float *__restrict__ g, int64_t n,
-                                                      float lr) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        W[e] = fmaf(-lr, g[e], W[e]);
-        g[e] = 0.f;
-    }
-}
-
 }  // namespace daisy
 
 using namespace daisy;
@@ -1882,14 +1176,13 @@ struct daisy_neumf_ctx {
     int64_t max_rows, U, I;
     int d, L, dm, model;
     int width[DAISY_NEUMF_MAX_LAYERS + 1];   // width[0] = 2*dm, width[l] = width[l-1]/2
-    void *arena;
-    size_t arena_bytes;
+    DeviceArena arena;
     float *X[DAISY_NEUMF_MAX_LAYERS + 1];    // X[0] = (dropped) concat input, X[l] = layer outputs
     float *G, *pred, *dpred, *DZ[2];
     uint16_t *W16[DAISY_NEUMF_MAX_LAYERS];   // bf16 copies of the MLP weights (precision level 2), refreshed per call
     uint16_t *W16T[DAISY_NEUMF_MAX_LAYERS];  // ... and their transposes [n_in][n_out]
     // scratch of the owner-based embedding scatter (allocated at its first use)
-    void *sc_arena;
+    DeviceArena sc_arena;
     int32_t *sc_ku, *sc_ki, *sc_val, *sc_ks, *sc_vs, *sc_cu, *sc_ci, *sc_cj;
     uint32_t *sc_ekey; uint2 *sc_esu; float2 *sc_w;
     float *sc_sum, *sc_sum2, *sc_sumg, *sc_sumg2, *sc_edge_vec, *sc_edge_b;      // row sums: MLP users, MLP items, GMF users, GMF items
@@ -1986,14 +1279,6 @@ static void reduce_slices(const float *ws, int nslices, int64_t len, float *out,
         hipLaunchKernelGGL(k_reduce_slices, dim3(grid_for(len, kBlock, 2048)), dim3(kBlock), 0, s, ws, nslices, len, out);
 }
 
-static inline hipStream_t NS(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-static uint32_t drop_threshold(float p) {
-    if (!(p > 0.f)) return 0u;
-    const double t = (double)p * 4294967296.0;
-    return (t >= 4294967295.0) ? 4294967295u : (uint32_t)t;
-}
-
 // precision level 2 applies when every GEMM of the call is made of whole tiles (else the call runs at level 1)
 static bool neumf_use_h(const daisy_neumf_ctx *ctx, int64_t R) {
     if (ctx->bf16 != 2 || ctx->model == DAISY_NEUMF_GMF || R % kGemmBM != 0) return false;
@@ -2057,8 +1342,7 @@ static int neumf_forward_rows(daisy_neumf_ctx *ctx, const daisy_neumf_params *p,
         // (... and none at all under the fused tower, which rounds W2 / W3 as it loads them into LDS)
         for (int l = neumf_use_tower(ctx, R, train, thresh) ? L + 1 : (neumf_use_fact(ctx, R, train, thresh) ? 2 : 1); l <= L; ++l) {
             const int64_t nw = (int64_t)ctx->width[l] * ctx->width[l - 1];
-            hipLaunchKernelGGL(k_to_bf16, dim3(grid_for(nw, kBlock * 4)), dim3(kBlock), 0, s, p->W[l - 1], nw,
-                               ctx->width[l - 1], ctx->W16[l - 1], ctx->W16T[l - 1]);
+            to_bf16_and_transpose(p->W[l - 1], nw, ctx->width[l - 1], ctx->W16[l - 1], ctx->W16T[l - 1], s);
         }
     }
     if (neumf_use_mid(ctx, R, train)) return DAISY_OK;     // (the gather, the layers and the predict layer happen in k_nmf_mid)
@@ -2148,45 +1432,32 @@ static int neumf_forward_rows(daisy_neumf_ctx *ctx, const daisy_neumf_params *p,
 }
 
 static int neumf_scatter_scratch(daisy_neumf_ctx *c) {
-    if (c->sc_arena) return DAISY_OK;
+    if (c->sc_arena.bytes()) return DAISY_OK;
     const size_t R = (size_t)c->max_rows + 1, dm = (size_t)c->dm;
     const size_t rows_max = (size_t)(c->U > c->I ? c->U : c->I);
     size_t chunks = (size_t)segsum_chunks((int64_t)R + 1, c->dm);
     const size_t ch2 = (size_t)segsum_chunks((int64_t)R + 1, c->d);
     if (ch2 > chunks) chunks = ch2;
     chunks += 2;
-    c->sc_tmp_bytes = sort_pairs_i32_temp_bytes((int64_t)R);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_ku = take(R * 4), o_ki = take(R * 4), o_val = take(R * 4), o_ks = take(R * 4), o_vs = take(R * 4);
-    const size_t o_cu = take((size_t)c->U * 4), o_ci = take((size_t)c->I * 4), o_cj = take((size_t)c->I * 4);
-    const size_t o_ek = take((R + 1) * 4), o_es = take((R + 1) * 8), o_w = take((R + 1) * 8);
-    const size_t o_sum = take(rows_max * dm * 4), o_sum2 = take(rows_max * dm * 4), o_sumg = take(rows_max * (size_t)c->d * 4),
-                 o_sumg2 = take(rows_max * (size_t)c->d * 4);
-    const size_t o_ev = take(2 * chunks * dm * 4), o_ei = take(2 * chunks * 4), o_eb = take(2 * chunks * 4), o_ew = take(chunks * 4);
-    const size_t o_tmp = take(c->sc_tmp_bytes);
-    hipError_t e = hipMalloc(&c->sc_arena, off);
-    if (e != hipSuccess) {
-        set_error("neumf: hipMalloc(%zu) of the scatter scratch failed: %s", off, hipGetErrorString(e));
-        c->sc_arena = nullptr;
-    c->cs_hist = nullptr;
-    c->cs_ent = nullptr;
-        return DAISY_ERR_HIP;
+    c->sc_tmp_bytes = sort_pairs_i32_temp_bytes_upto((int64_t)R);
+    DeviceArena &a = c->sc_arena;
+    a.add(&c->sc_ku, R * 4); a.add(&c->sc_ki, R * 4); a.add(&c->sc_val, R * 4); a.add(&c->sc_ks, R * 4); a.add(&c->sc_vs, R * 4);
+    a.add(&c->sc_cu, (size_t)c->U * 4); a.add(&c->sc_ci, (size_t)c->I * 4); a.add(&c->sc_cj, (size_t)c->I * 4);
+    a.add(&c->sc_ekey, (R + 1) * 4); a.add(&c->sc_esu, (R + 1) * 8); a.add(&c->sc_w, (R + 1) * 8);
+    a.add(&c->sc_sum, rows_max * dm * 4); a.add(&c->sc_sum2, rows_max * dm * 4);
+    a.add(&c->sc_sumg, rows_max * (size_t)c->d * 4); a.add(&c->sc_sumg2, rows_max * (size_t)c->d * 4);
+    a.add(&c->sc_edge_vec, 2 * chunks * dm * 4); a.add(&c->sc_edge_item, 2 * chunks * 4); a.add(&c->sc_edge_b, 2 * chunks * 4);
+    a.add(&c->sc_edge_whole, chunks * 4);
+    a.add(&c->sc_tmp, c->sc_tmp_bytes);
+    if (int rc = a.alloc("neumf: the scatter scratch")) {
+        a.release();
+        return rc;
     }
-    char *b = (char *)c->sc_arena;
-    c->sc_ku = (int32_t *)(b + o_ku); c->sc_ki = (int32_t *)(b + o_ki); c->sc_val = (int32_t *)(b + o_val);
-    c->sc_ks = (int32_t *)(b + o_ks); c->sc_vs = (int32_t *)(b + o_vs);
-    c->sc_cu = (int32_t *)(b + o_cu); c->sc_ci = (int32_t *)(b + o_ci); c->sc_cj = (int32_t *)(b + o_cj);
-    c->sc_ekey = (uint32_t *)(b + o_ek); c->sc_esu = (uint2 *)(b + o_es); c->sc_w = (float2 *)(b + o_w);
-    c->sc_sum = (float *)(b + o_sum); c->sc_sum2 = (float *)(b + o_sum2); c->sc_sumg = (float *)(b + o_sumg);
-    c->sc_sumg2 = (float *)(b + o_sumg2);
-    c->sc_edge_vec = (float *)(b + o_ev); c->sc_edge_item = (int32_t *)(b + o_ei); c->sc_edge_b = (float *)(b + o_eb);
-    c->sc_edge_whole = (int32_t *)(b + o_ew);
-    c->sc_tmp = b + o_tmp;
     // the counts and the row-sum table are kept all-zero between calls by the kernels that consume them
-    e = hipMemset(b + o_cu, 0, o_ek - o_cu);
-    if (e == hipSuccess) e = hipMemset(b + o_sum, 0, (o_sumg2 - o_sum) + rows_max * (size_t)c->d * 4);      // (the four sum tables: contiguous)
-    if (e != hipSuccess) { set_error("neumf: hipMemset of the scatter scratch failed"); return DAISY_ERR_HIP; }
+    // (the three count arrays are adjacent slots, and so are the four sum tables)
+    hipError_t e = hipMemset(c->sc_cu, 0, (size_t)((char *)c->sc_ekey - (char *)c->sc_cu));
+    if (e == hipSuccess) e = hipMemset(c->sc_sum, 0, (size_t)((char *)c->sc_sumg2 - (char *)c->sc_sum) + rows_max * (size_t)c->d * 4);
+    if (e != hipSuccess) { a.release(); set_error("neumf: hipMemset of the scatter scratch failed"); return DAISY_ERR_HIP; }
     return DAISY_OK;
 }
 
@@ -2405,44 +1676,33 @@ int daisy_neumf_ctx_create(daisy_neumf_ctx **out, int64_t max_rows, int32_t fact
     c->max_rows = max_rows; c->U = user_num; c->I = item_num;
     c->d = factors; c->L = num_layers; c->model = model;
     c->bf16 = 0;
-    c->sc_arena = nullptr;
     c->det_ws = nullptr; c->det_ws_floats = 0;
     c->dm = factors << (num_layers - 1);
     c->width[0] = 2 * c->dm;
     for (int l = 1; l <= num_layers; ++l) c->width[l] = c->width[l - 1] / 2;
     c->mid_fits = neumf_mid_fits(c->L, c->width, c->d);
     c->mid_aligned = false;
-    size_t off = 0, ox[DAISY_NEUMF_MAX_LAYERS + 1];
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    for (int l = 0; l <= num_layers; ++l) ox[l] = take((size_t)max_rows * c->width[l] * 4);
-    const size_t og = take((size_t)max_rows * factors * 4), op = take((size_t)max_rows * 4),
-                 od = take((size_t)max_rows * 4);
-    const size_t oz0 = take((size_t)max_rows * c->width[0] * 4), oz1 = take((size_t)max_rows * c->width[0] * 4);
-    size_t ow[DAISY_NEUMF_MAX_LAYERS];
-    for (int l = 1; l <= num_layers; ++l) ow[l - 1] = take((size_t)c->width[l] * c->width[l - 1] * 2 * 2);
-    c->arena_bytes = off;
-    hipError_t e = hipMalloc(&c->arena, off);
-    if (e != hipSuccess) {
-        set_error("neumf_ctx_create: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+    DeviceArena &a = c->arena;
+    for (int l = 0; l <= num_layers; ++l) a.add(&c->X[l], (size_t)max_rows * c->width[l] * 4);
+    a.add(&c->G, (size_t)max_rows * factors * 4);
+    a.add(&c->pred, (size_t)max_rows * 4);
+    a.add(&c->dpred, (size_t)max_rows * 4);
+    a.add(&c->DZ[0], (size_t)max_rows * c->width[0] * 4);
+    a.add(&c->DZ[1], (size_t)max_rows * c->width[0] * 4);
+    for (int l = 1; l <= num_layers; ++l) a.add(&c->W16[l - 1], (size_t)c->width[l] * c->width[l - 1] * 2 * 2);
+    if (int rc = a.alloc("neumf_ctx_create")) {
         delete c;
-        return DAISY_ERR_HIP;
+        return rc;
     }
-    char *base = (char *)c->arena;
-    for (int l = 0; l <= num_layers; ++l) c->X[l] = (float *)(base + ox[l]);
-    c->G = (float *)(base + og); c->pred = (float *)(base + op); c->dpred = (float *)(base + od);
-    c->DZ[0] = (float *)(base + oz0); c->DZ[1] = (float *)(base + oz1);
-    for (int l = 1; l <= num_layers; ++l) {
-        c->W16[l - 1] = (uint16_t *)(base + ow[l - 1]);
-        c->W16T[l - 1] = c->W16[l - 1] + (size_t)c->width[l] * c->width[l - 1];
-    }
+    for (int l = 1; l <= num_layers; ++l) c->W16T[l - 1] = c->W16[l - 1] + (size_t)c->width[l] * c->width[l - 1];
     *out = c;
     return DAISY_OK;
 }
 
 int daisy_neumf_ctx_destroy(daisy_neumf_ctx *ctx) {
     if (!ctx) return DAISY_OK;
-    if (ctx->arena) (void)hipFree(ctx->arena);
-    if (ctx->sc_arena) (void)hipFree(ctx->sc_arena);
+    ctx->arena.release();
+    ctx->sc_arena.release();
     if (ctx->cs_hist) (void)hipFree(ctx->cs_hist);
     if (ctx->cs_ent) (void)hipFree(ctx->cs_ent);
     if (ctx->det_ws) (void)hipFree(ctx->det_ws);
@@ -2451,7 +1711,7 @@ int daisy_neumf_ctx_destroy(daisy_neumf_ctx *ctx) {
     return DAISY_OK;
 }
 
-size_t daisy_neumf_ctx_bytes(const daisy_neumf_ctx *ctx) { return ctx ? ctx->arena_bytes : 0; }
+size_t daisy_neumf_ctx_bytes(const daisy_neumf_ctx *ctx) { return ctx ? ctx->arena.bytes() : 0; }
 
 int daisy_neumf_ctx_set_precision(daisy_neumf_ctx *ctx, int32_t bf16_gemm) {
     DAISY_CHECK_ARG(ctx != nullptr, "neumf_ctx_set_precision: NULL context");
@@ -2464,7 +1724,7 @@ int daisy_neumf_scores(daisy_neumf_ctx *ctx, const daisy_neumf_params *params, c
                        const int64_t *items, int64_t n, int64_t C, float *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && params && users && out && n > 0 && C >= 0, "neumf_scores: bad argument");
     DAISY_CHECK_ARG(items || C == 0, "neumf_scores: items is NULL but C != 0");
-    hipStream_t s = NS(stream);
+    hipStream_t s = as_stream(stream);
     for (int64_t base = 0; base < n; base += ctx->max_rows) {
         const int64_t R = (n - base < ctx->max_rows) ? (n - base) : ctx->max_rows;
         PairSrc src{};
@@ -2488,10 +1748,10 @@ int daisy_neumf_step_grads(daisy_neumf_ctx *ctx, const daisy_neumf_params *param
     const int64_t R = pointwise ? B : 2 * B;
     DAISY_CHECK_ARG(R <= ctx->max_rows, "neumf_step_grads: %lld rows exceed the context's %lld",
                     (long long)R, (long long)ctx->max_rows);
-    hipStream_t s = NS(stream);
+    hipStream_t s = as_stream(stream);
     const daisy_neumf_params &p = *params, &g = *grads;
     const int d = ctx->d, dm = ctx->dm, L = ctx->L, model = ctx->model;
-    const uint32_t thresh = (model == DAISY_NEUMF_GMF) ? 0u : drop_threshold(dropout_p);
+    const uint32_t thresh = (model == DAISY_NEUMF_GMF) ? 0u : keep_threshold(dropout_p);
     const float scale = thresh ? 1.f / (1.f - dropout_p) : 1.f;
     {
         uintptr_t bits = (uintptr_t)p.Wp | (uintptr_t)p.uG | (uintptr_t)p.iG | (uintptr_t)p.uM | (uintptr_t)p.iM;
@@ -2682,9 +1942,7 @@ int daisy_neumf_fit_epoch(daisy_neumf_ctx *ctx, const daisy_neumf_params *params
                           double *stats, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && params && grads && u && i && j && stats && W && g && n > 0 && batch > 0 && n_flat > 0 && step0 >= 0,
                     "neumf_fit_epoch: bad argument");
-    DAISY_CHECK_ARG(optimizer >= 0 && optimizer <= 3, "neumf_fit_epoch: optimizer=%d (0 sgd, 1 adam, 2 adagrad, 3 rmsprop)", optimizer);
-    DAISY_CHECK_ARG(optimizer == 0 || state0, "neumf_fit_epoch: optimizer %d needs its state", optimizer);
-    DAISY_CHECK_ARG(optimizer != 1 || state1, "neumf_fit_epoch: Adam needs both moments");
+    if (int rc = dense_opt_check("neumf_fit_epoch", optimizer, state0, state1)) return rc;
     // the reference's loop (AbstractRecommender.py:119-128) over the epoch's batches, issued from here: at 256 samples per step
     // a step is ~40 us of kernels, less than the Python of one iteration around two library calls
     int64_t step = step0;
@@ -2694,66 +1952,9 @@ int daisy_neumf_fit_epoch(daisy_neumf_ctx *ctx, const daisy_neumf_params *params
         int rc = daisy_neumf_step_grads(ctx, params, grads, u + s0, i + s0, j + s0, B, loss_type, gamma, reg_1, reg_2, dropout_p,
                                         seed_hi | (uint64_t)step, stats, stream);
         if (rc) return rc;
-        if (optimizer == 0) rc = daisy_sgd_dense(W, g, n_flat, lr, stream);
-        else if (optimizer == 1) rc = daisy_adam_dense(W, g, state0, state1, n_flat, lr, 0.9f, 0.999f, 1e-8f, step, stream);
-        else if (optimizer == 2) rc = daisy_adagrad_dense(W, g, state0, n_flat, lr, 1e-10f, stream);
-        else rc = daisy_rmsprop_dense(W, g, state0, n_flat, lr, 0.99f, 1e-8f, stream);
-        if (rc) return rc;
+        // (Adam's step count here is the dropout step counter itself: this entry point has no separate opt_step0)
+        if ((rc = dense_opt_step(optimizer, W, g, state0, state1, n_flat, lr, step, stream))) return rc;
     }
-    return DAISY_OK;
-}
-
-int daisy_gemm_nt_bf16(const uint16_t *A, const uint16_t *B, uint16_t *C, int64_t M, int32_t N, int32_t K,
-                       daisy_stream_t stream) {
-    DAISY_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0, "gemm_nt_bf16: bad argument");
-    GemmOp op{};
-    op.A16 = A; op.sam = K; op.sak = 1;
-    op.B16 = B; op.sbn = K; op.sbk = 1;
-    op.C16 = C; op.ldc = N;
-    op.M = M; op.N = N; op.K = K; op.k_chunk = K;
-    DAISY_CHECK_ARG(gemm_h_ok(op), "gemm_nt_bf16: needs M %% 128 == 0, N %% 64 == 0 (128 when N > 64), K %% 32 == 0, 16-byte aligned rows");
-    launch_gemm_h<EPI_GATE>(op, NS(stream));          // no gate tensor: a plain bf16 store
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_gemm_tn_bf16(const uint16_t *At, const uint16_t *Bt, float *C, int64_t M, int32_t N, int64_t K,
-                       int64_t k_chunk, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(At && Bt && C && M > 0 && N > 0 && K > 0 && k_chunk > 0, "gemm_tn_bf16: bad argument");
-    GemmOp op{};                         // the weight-gradient layout: both operands [K][rows], rows contiguous
-    op.A16 = At; op.sam = 1; op.sak = M;
-    op.B16 = Bt; op.sbn = 1; op.sbk = N;
-    op.C = C; op.ldc = N;
-    op.M = M; op.N = N; op.K = K; op.k_chunk = k_chunk;
-    DAISY_CHECK_ARG(gemm_h_ok(op), "gemm_tn_bf16: needs M %% 128 == 0, N %% 64 == 0 (128 when N > 64), K and k_chunk %% 32 == 0, "
-                                   "M and N %% 8 == 0, 16-byte aligned operands");
-    launch_gemm_h<EPI_ATOMIC>(op, NS(stream));
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_sgd_dense(float *W, float *g, int64_t n, float lr, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(W && g && n > 0, "sgd_dense: bad argument");
-    hipLaunchKernelGGL(k_sgd_dense, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, NS(stream), W, g, n, lr);
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_gemm_nt_f32(const float *A, const float *B, float *C, int64_t M, int32_t N, int32_t K,
-                      daisy_stream_t stream) {
-    return daisy_gemm_nt(A, B, C, M, N, K, 0, stream);
-}
-
-int daisy_gemm_nt(const float *A, const float *B, float *C, int64_t M, int32_t N, int32_t K, int32_t bf16,
-                  daisy_stream_t stream) {
-    DAISY_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0, "gemm_nt: bad argument");
-    GemmOp op{};
-    op.bf16 = bf16 ? 1 : 0;
-    op.A = A; op.sam = K; op.sak = 1;
-    op.B = B; op.sbn = K; op.sbk = 1;
-    op.C = C; op.ldc = N; op.M = M; op.N = N; op.K = K; op.k_chunk = K;
-    launch_gemm<EPI_STORE>(op, NS(stream));
-    DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }
 

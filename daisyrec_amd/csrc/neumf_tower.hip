@@ -26,6 +26,7 @@
 // one ds_write_b64 - instead of 16 rows of one feature.
 #include <stdlib.h>
 
+#include "mfma.h"
 #include "neumf_internal.h"
 
 namespace daisy {

@@ -16,7 +16,7 @@
 // No float atomics touch a result: two runs of a step give the same bits.  Rows of one workgroup tile never straddle
 // the two calls, so every per-call column reduction is a sum over whole tiles.
 #include "common.h"
-#include "neumf_internal.h"
+#include "pairs.h"
 
 namespace daisy {
 
@@ -742,8 +742,7 @@ struct daisy_nfm_ctx {
     int64_t max_rows;    // rows of one forward call
     int d, L, act, bn;
     int64_t user_num, item_num;
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
+    DeviceArena arena;
     float *Z, *G, *G2, *pred, *dpred, *dbs, *stat, *k12, *wpart, *wws;
     double *part, *regpart;
     int32_t *kin, *kout, *vin, *vout;
@@ -759,7 +758,6 @@ int64_t nf_wchunk_rows(int64_t R) {
     int64_t rpc = (R + kNfWChunks - 1) / kNfWChunks;
     return (rpc + kNfTR - 1) / kNfTR * kNfTR;
 }
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 NfStage nf_stage(const daisy_nfm_ctx *c, const daisy_nfm_params *p, const daisy_nfm_bn_state *bn, int s, int64_t R, bool batch_stats,
                  uint32_t thresh, float scale) {
@@ -852,42 +850,30 @@ int daisy_nfm_ctx_create(daisy_nfm_ctx **out, int64_t max_rows, int32_t factors,
     c->item_num = item_num;
     const int64_t R = 2 * max_rows, d = factors, T = 2 * nf_tiles_per_call(max_rows);
     const int64_t nch = kNfWChunks;         // (the chunk count of a step is at most this, not monotonic in R)
-    // (rocPRIM switches from merge sort to Onesweep above 262 144 items: a smaller step may need the larger buffer)
-    c->sort_bytes = sort_pairs_i32_temp_bytes(R);
-    const size_t merge_bytes = sort_pairs_i32_temp_bytes(R < 262144 ? R : 262144);
-    if (merge_bytes > c->sort_bytes) c->sort_bytes = merge_bytes;
-    const size_t sizes[] = {al((size_t)(c->L + 1) * R * d * 4), al((size_t)R * d * 4), al((size_t)R * d * 4), al(R * 4), al(R * 4),
-                            al(R * 4), al((size_t)(c->L + 1) * 4 * d * 4), al(4 * d * 4), al((size_t)T * (d + 1) * 4),
-                            al((size_t)nch * (d * d + d) * 4), al((size_t)T * 2 * d * 8), al((size_t)T * 4 * 8), al(R * 4), al(R * 4),
-                            al(R * 4), al(R * 4), al(c->sort_bytes)};
-    size_t total = 0;
-    for (size_t x : sizes) total += x;
-    hipError_t e = hipMalloc(&c->arena, total);
-    if (e != hipSuccess) {
+    c->sort_bytes = sort_pairs_i32_temp_bytes_upto(R);
+    DeviceArena &a = c->arena;
+    a.add(&c->Z, (size_t)(c->L + 1) * R * d * 4); a.add(&c->G, (size_t)R * d * 4); a.add(&c->G2, (size_t)R * d * 4);
+    a.add(&c->pred, R * 4); a.add(&c->dpred, R * 4); a.add(&c->dbs, R * 4);
+    a.add(&c->stat, (size_t)(c->L + 1) * 4 * d * 4); a.add(&c->k12, 4 * d * 4);
+    a.add(&c->wpart, (size_t)T * (d + 1) * 4); a.add(&c->wws, (size_t)nch * (d * d + d) * 4);
+    a.add(&c->part, (size_t)T * 2 * d * 8); a.add(&c->regpart, (size_t)T * 4 * 8);
+    a.add(&c->kin, R * 4); a.add(&c->kout, R * 4); a.add(&c->vin, R * 4); a.add(&c->vout, R * 4);
+    a.add(&c->sort_tmp, c->sort_bytes);
+    if (int rc = a.alloc("nfm_ctx_create")) {
         delete c;
-        set_error("nfm_ctx_create: hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
-        return DAISY_ERR_HIP;
+        return rc;
     }
-    c->arena_bytes = total;
     const int lds = (int)nf_lds_bytes(factors);
     const void *lds_kernels[] = {(const void *)k_nfm_gather, (const void *)k_nfm_linear, (const void *)k_nfm_head_bwd,
                                  (const void *)k_nfm_bwd_act, (const void *)k_nfm_wgrad, (const void *)k_nfm_small_step};
     for (const void *kf : lds_kernels) {
-        e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        const hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) {
-            (void)hipFree(c->arena);
+            c->arena.release();
             delete c;
             set_error("nfm_ctx_create: hipFuncSetAttribute(%d B of LDS) failed: %s", lds, hipGetErrorString(e));
             return DAISY_ERR_HIP;
         }
-    }
-    char *q = static_cast<char *>(c->arena);
-    void **slots[] = {(void **)&c->Z, (void **)&c->G, (void **)&c->G2, (void **)&c->pred, (void **)&c->dpred, (void **)&c->dbs,
-                      (void **)&c->stat, (void **)&c->k12, (void **)&c->wpart, (void **)&c->wws, (void **)&c->part,
-                      (void **)&c->regpart, (void **)&c->kin, (void **)&c->kout, (void **)&c->vin, (void **)&c->vout, &c->sort_tmp};
-    for (size_t k = 0; k < sizeof(sizes) / sizeof(sizes[0]); ++k) {
-        *slots[k] = q;
-        q += sizes[k];
     }
     *out = c;
     return DAISY_OK;
@@ -895,12 +881,12 @@ int daisy_nfm_ctx_create(daisy_nfm_ctx **out, int64_t max_rows, int32_t factors,
 
 int daisy_nfm_ctx_destroy(daisy_nfm_ctx *ctx) {
     if (!ctx) return DAISY_OK;
-    if (ctx->arena) (void)hipFree(ctx->arena);
+    ctx->arena.release();
     delete ctx;
     return DAISY_OK;
 }
 
-size_t daisy_nfm_ctx_bytes(const daisy_nfm_ctx *ctx) { return ctx ? ctx->arena_bytes : 0; }
+size_t daisy_nfm_ctx_bytes(const daisy_nfm_ctx *ctx) { return ctx ? ctx->arena.bytes() : 0; }
 
 int daisy_nfm_ctx_set_path(daisy_nfm_ctx *ctx, int32_t path) {
     DAISY_CHECK_ARG(ctx, "nfm_ctx_set_path: ctx is NULL");
@@ -924,7 +910,7 @@ int daisy_nfm_step_grads(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, con
     if (int rc = nf_check_params(ctx, params, "nfm_step_grads")) return rc;
     if (int rc = nf_check_params(ctx, grads, "nfm_step_grads (grads)")) return rc;
     if (int rc = nf_check_bn(ctx, bn, "nfm_step_grads")) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     const daisy_nfm_params &p = *params, &g = *grads;
     const int d = ctx->d, L = ctx->L;
     NfStep a{};
@@ -1030,9 +1016,8 @@ int daisy_nfm_step_grads(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, con
         hipLaunchKernelGGL(k_nfm_keys, dim3(grid_for(R, kBlock)), dim3(kBlock), 0, s, a.src, R, side, ctx->kin, ctx->vin);
         DAISY_LAUNCH_CHECK();
         const int64_t rows = side ? ctx->item_num : ctx->user_num;
-        int bits = 1;
-        while (bits < 31 && (1ll << bits) < rows) ++bits;
-        if (int rc = sort_pairs_i32(ctx->sort_tmp, ctx->sort_bytes, ctx->kin, ctx->kout, ctx->vin, ctx->vout, R, bits, s)) return rc;
+        if (int rc = sort_pairs_i32(ctx->sort_tmp, ctx->sort_bytes, ctx->kin, ctx->kout, ctx->vin, ctx->vout, R, bits_for(rows), s))
+            return rc;
         hipLaunchKernelGGL(k_nfm_embed_grad, dim3(grid_for(R * (d + 1), kBlock, kMaxGridSparse)), dim3(kBlock), 0, s, ctx->kout,
                            ctx->vout, R, side, a.src, B, d, p.P, p.Q, G, ctx->dbs, reg_1, reg_2, stats, side ? g.Q : g.P,
                            side ? g.ib : g.ub);
@@ -1048,9 +1033,7 @@ int daisy_nfm_fit_epoch(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, cons
                         float *state0, float *state1, int64_t n_flat, double *stats, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && params && grads && u && i && j && stats && W && g && n > 0 && batch > 0 && n_flat > 0 && step0 >= 0 &&
                     opt_step0 >= 0, "nfm_fit_epoch: bad argument");
-    DAISY_CHECK_ARG(optimizer >= 0 && optimizer <= 3, "nfm_fit_epoch: optimizer=%d (0 sgd, 1 adam, 2 adagrad, 3 rmsprop)", optimizer);
-    DAISY_CHECK_ARG(optimizer == 0 || state0, "nfm_fit_epoch: optimizer %d needs its state", optimizer);
-    DAISY_CHECK_ARG(optimizer != 1 || state1, "nfm_fit_epoch: Adam needs both moments");
+    if (int rc = dense_opt_check("nfm_fit_epoch", optimizer, state0, state1)) return rc;
     DAISY_CHECK_ARG(batch <= ctx->max_rows, "nfm_fit_epoch: batch=%lld > max_rows=%lld", (long long)batch, (long long)ctx->max_rows);
     DAISY_CHECK_ARG(!ctx->bn || n % batch != 1,
                     "nfm_fit_epoch: Expected more than 1 value per channel when training (BatchNorm, last batch of 1 row)");
@@ -1062,11 +1045,7 @@ int daisy_nfm_fit_epoch(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, cons
         int rc = daisy_nfm_step_grads(ctx, params, grads, bn, u + s0, i + s0, j + s0, B, loss_type, gamma, reg_1, reg_2, dropout_p,
                                       seed_hi | (uint64_t)step, stats, stream);
         if (rc) return rc;
-        if (optimizer == 0) rc = daisy_sgd_dense(W, g, n_flat, lr, stream);
-        else if (optimizer == 1) rc = daisy_adam_dense(W, g, state0, state1, n_flat, lr, 0.9f, 0.999f, 1e-8f, t, stream);
-        else if (optimizer == 2) rc = daisy_adagrad_dense(W, g, state0, n_flat, lr, 1e-10f, stream);
-        else rc = daisy_rmsprop_dense(W, g, state0, n_flat, lr, 0.99f, 1e-8f, stream);
-        if (rc) return rc;
+        if ((rc = dense_opt_step(optimizer, W, g, state0, state1, n_flat, lr, t, stream))) return rc;
     }
     return DAISY_OK;
 }
@@ -1081,7 +1060,7 @@ int daisy_nfm_scores(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const d
     DAISY_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "nfm_scores: dropout=%g (0 <= p < 1)", (double)dropout_p);
     if (int rc = nf_check_params(ctx, params, "nfm_scores")) return rc;
     if (int rc = nf_check_bn(ctx, bn, "nfm_scores", train != 0)) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     PairSrc src{};
     src.users = users;
     src.items = items;

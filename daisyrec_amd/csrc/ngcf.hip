@@ -10,7 +10,7 @@
 // Everything is fp32 like the reference.  The sparse products (X = A_hat E and its transpose) are
 // daisy_lgcn_spmm_ex in lightgcn.hip.
 #include "common.h"
-#include "neumf_internal.h"
+#include "mfma.h"
 
 namespace daisy {
 
@@ -351,7 +351,6 @@ static bool width_ok(int32_t d) { return d >= 1 && d <= DAISY_NGCF_MAX_WIDTH; }
 
 using namespace daisy;
 
-static inline hipStream_t NS(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 #define NGCF_CHECK_SHAPE(fn, n, d_in, d_out)                                                                     \
     DAISY_CHECK_ARG((n) > 0 && width_ok(d_in) && width_ok(d_out),                                              \
@@ -363,7 +362,7 @@ extern "C" {
 int daisy_dropout_mask(uint64_t seed, uint32_t stream_id, int64_t n, float p, uint8_t *out, daisy_stream_t stream) {
     DAISY_CHECK_ARG(out != nullptr && n > 0, "dropout_mask: NULL output or n <= 0");
     DAISY_CHECK_ARG(p >= 0.f && p < 1.f, "dropout_mask: p=%g outside [0, 1)", (double)p);
-    hipLaunchKernelGGL(k_dropout_mask, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, NS(stream), seed, stream_id, n,
+    hipLaunchKernelGGL(k_dropout_mask, dim3(grid_for(n, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), seed, stream_id, n,
                        keep_threshold(p), out);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -387,7 +386,7 @@ int daisy_ngcf_layer_forward(const float *E, int64_t lde, const float *X, const 
             DAISY_NGCF_MESS_STREAM + (uint32_t)layer, 1.f, seed};
     a.scale = a.thresh ? 1.f / (1.f - mess_p) : 1.f;
     const dim3 grid(grid_for(n, kNgRows)), block(kBlock);
-    hipStream_t s = NS(stream);
+    hipStream_t s = as_stream(stream);
     switch ((d_out + 31) / 32) {
         case 1: hipLaunchKernelGGL(k_ngcf_layer_fwd<1>, grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL(k_ngcf_layer_fwd<2>, grid, block, 0, s, a); break;
@@ -415,7 +414,7 @@ int daisy_ngcf_layer_backward(const float *dY, int64_t ldd, const float *Y, int6
                     "ngcf_layer_backward: dE, dX and dY must be distinct buffers");
     DAISY_CHECK_ARG(mess_p >= 0.f && mess_p < 1.f, "ngcf_layer_backward: mess_p=%g outside [0, 1)", (double)mess_p);
     DAISY_CHECK_ARG(layer >= 0, "ngcf_layer_backward: layer < 0");
-    hipStream_t s = NS(stream);
+    hipStream_t s = as_stream(stream);
     float *dZ = ws;
     float *slab = (float *)((char *)ws + align_up((size_t)n * d_out * 4));
     NgBwd a{dY, ldd, Y, ldy, norm, E, lde, X, W1, W2, gprev, ldg, dE, dX, dZ, n, d_in, d_out,
@@ -451,7 +450,7 @@ int daisy_ngcf_wgrad_reduce(const float *ws, int64_t n, int32_t d_in, int32_t d_
     DAISY_CHECK_ARG(ws && dW1 && db1 && dW2 && db2, "ngcf_wgrad_reduce: NULL argument");
     const float *slab = (const float *)((const char *)ws + align_up((size_t)n * d_out * 4));
     const int64_t total = (int64_t)d_out * (2 * d_in + 1);
-    hipLaunchKernelGGL(k_ngcf_wgrad_sum, dim3(grid_for(total, kBlock)), dim3(kBlock), 0, NS(stream), slab,
+    hipLaunchKernelGGL(k_ngcf_wgrad_sum, dim3(grid_for(total, kBlock)), dim3(kBlock), 0, as_stream(stream), slab,
                        wgrad_chunks(n), (int)d_in, (int)d_out, dW1, db1, dW2, db2);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;

@@ -1,0 +1,29 @@
+// The (user, item) pair layouts a kernel can be handed: a training batch (u, i, j) or one of the three scoring layouts.
+// Used by NeuMF (neumf.hip) and NFM (nfm.hip).
+#pragma once
+#include "common.h"
+
+namespace daisy {
+
+// the three pair layouts of daisy_neumf_scores plus the training batch
+struct PairSrc {
+    const int32_t *u, *i, *j;     // training: row r < B -> (u[r], i[r]); r >= B -> (u[r-B], j[r-B])
+    int64_t B;
+    const int64_t *users, *items; // scoring
+    int64_t C;                    // > 0: user of pair e = users[e / C];  0 with items == NULL: (users[0], e)
+    int64_t base;                 // first pair of this chunk
+};
+__device__ __forceinline__ void pair_ids(const PairSrc &s, int64_t r, int64_t &user, int64_t &item) {
+    if (s.u) {
+        const int64_t b = (r < s.B) ? r : r - s.B;
+        user = s.u[b];
+        item = (r < s.B) ? s.i[b] : s.j[b];
+    } else {
+        const int64_t e = s.base + r;
+        if (!s.items) { user = s.users[0]; item = e; }
+        else if (s.C > 0) { user = s.users[e / s.C]; item = s.items[e]; }
+        else { user = s.users[e]; item = s.items[e]; }
+    }
+}
+
+}  // namespace daisy

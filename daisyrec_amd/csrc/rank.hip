@@ -88,7 +88,6 @@ __global__ void k_take_topk(const int64_t *__restrict__ sorted_ids, int64_t B, i
     }
 }
 
-static inline hipStream_t S(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 __global__ void k_iota_i64(int64_t n, int64_t *__restrict__ out) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -114,7 +113,7 @@ int daisy_fm_predict(const float *P, const float *Q, const float *u_bias, const 
     int rc = dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         hipLaunchKernelGGL((k_predict<C>), dim3(grid_for(B, C::GROUPS_PER_BLOCK)), dim3(kBlock), 0,
-                           S(stream), P, Q, (int)d, u, i, B, out, u_bias, i_bias, bias);
+                           as_stream(stream), P, Q, (int)d, u, i, B, out, u_bias, i_bias, bias);
         return DAISY_OK;
     });
     if (rc) return rc;
@@ -146,7 +145,7 @@ int daisy_fm_rank_topk(const float *P, const float *Q, const float *u_bias, cons
                     "mf_rank_topk: bad sizes B=%lld C=%lld topk=%d", (long long)B, (long long)C, topk);
     DAISY_CHECK_ARG(workspace_bytes >= daisy_mf_rank_workspace_bytes(B, C),
                     "mf_rank_topk: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const size_t n = (size_t)B * (size_t)C;
     char *w = (char *)workspace;
     float *scores = (float *)w;             w += align_up(n * 4);
@@ -194,7 +193,7 @@ int daisy_fm_full_rank(const float *P, const float *Q, const float *u_bias, cons
                     "mf_full_rank: bad argument");
     DAISY_CHECK_ARG(workspace_bytes >= daisy_mf_full_rank_workspace_bytes(item_num),
                     "mf_full_rank: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const size_t n = (size_t)item_num;
     char *w = (char *)workspace;
     float *scores = (float *)w;          w += align_up(n * 4);
@@ -224,7 +223,7 @@ int daisy_topk_from_scores(const float *scores, const int64_t *cands, int64_t B,
     DAISY_CHECK_ARG(B > 0 && C > 0 && topk > 0 && topk <= C && B * C < ((int64_t)1 << 31),
                     "topk_from_scores: bad sizes B=%lld C=%lld topk=%d", (long long)B, (long long)C, topk);
     DAISY_CHECK_ARG(workspace_bytes >= daisy_mf_rank_workspace_bytes(B, C), "topk_from_scores: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const size_t n = (size_t)B * (size_t)C;
     char *w = (char *)workspace;
     w += align_up(n * 4);                                 // (the slot the MF path keeps its scores in)
@@ -245,7 +244,7 @@ int daisy_full_topk_from_scores(const float *scores, int64_t item_num, int32_t t
                     "full_topk_from_scores: bad argument");
     DAISY_CHECK_ARG(workspace_bytes >= daisy_mf_full_rank_workspace_bytes(item_num),
                     "full_topk_from_scores: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const size_t n = (size_t)item_num;
     char *w = (char *)workspace;
     w += align_up(n * 4);

@@ -164,7 +164,6 @@ __global__ void k_perm_keys(int64_t n, uint64_t seed, uint64_t stream, uint64_t 
     }
 }
 
-static inline hipStream_t S(daisy_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 constexpr uint64_t kStreamInteraction = 1ull << 63;
 constexpr uint64_t kStreamPerm = 1ull << 62;
 
@@ -185,7 +184,7 @@ int daisy_build_user_csr(const int32_t *users, const int32_t *items, int64_t n, 
     DAISY_CHECK_ARG(users && items && indptr && csr_items && workspace && n > 0 && user_num > 0,
                     "build_user_csr: bad argument");
     DAISY_CHECK_ARG(workspace_bytes >= daisy_csr_workspace_bytes(n), "build_user_csr: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     char *w = (char *)workspace;
     uint64_t *kin = (uint64_t *)w;   w += align_up((size_t)n * 8);
     uint64_t *kout = (uint64_t *)w;  w += align_up((size_t)n * 8);
@@ -208,7 +207,7 @@ int daisy_sample_neg_per_user(const int64_t *indptr, const int32_t *csr_items, i
                     "sample_neg_per_user: bad argument");
     DAISY_CHECK_ARG(epoch < kStreamPerm, "sample_neg_per_user: epoch out of range");
     hipLaunchKernelGGL(k_sample_per_user, dim3(grid_for(user_num * num_ng, kBlock)), dim3(kBlock), 0,
-                       S(stream), indptr, csr_items, user_num, item_num, (int)num_ng, seed, epoch, js);
+                       as_stream(stream), indptr, csr_items, user_num, item_num, (int)num_ng, seed, epoch, js);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }
@@ -219,7 +218,7 @@ int daisy_skipgram_samples(const int32_t *seq_items, const int32_t *seq_user, co
                            int32_t *bad_flag, daisy_stream_t stream) {
     DAISY_CHECK_ARG(seq_items && seq_user && seq_ptr && row_offsets && ur_indptr && ur_items && out && bad_flag &&
                         n > 0 && context_window > 0 && item_num > 0, "skipgram_samples: bad argument");
-    hipLaunchKernelGGL(k_skipgram_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, S(stream), seq_items, seq_user, seq_ptr,
+    hipLaunchKernelGGL(k_skipgram_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, as_stream(stream), seq_items, seq_user, seq_ptr,
                        row_offsets, n, (int)context_window, ur_indptr, ur_items, item_num, seed, stream_id, out, bad_flag);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -229,7 +228,7 @@ int daisy_sample_categorical(const double *cdf, int64_t item_num, int64_t rows, 
                              uint64_t stream_id, int32_t *out, int32_t ld, int32_t col0, daisy_stream_t stream) {
     DAISY_CHECK_ARG(cdf && out && item_num > 0 && rows > 0 && k > 0 && ld >= col0 + k && col0 >= 0,
                     "sample_categorical: bad argument");
-    hipLaunchKernelGGL(k_sample_categorical, dim3(grid_for(rows * k, kBlock)), dim3(kBlock), 0, S(stream), cdf, item_num,
+    hipLaunchKernelGGL(k_sample_categorical, dim3(grid_for(rows * k, kBlock)), dim3(kBlock), 0, as_stream(stream), cdf, item_num,
                        rows, (int)k, seed, stream_id, out, (int)ld, (int)col0);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -238,7 +237,7 @@ int daisy_sample_categorical(const double *cdf, int64_t item_num, int64_t rows, 
 int daisy_expand_triples(const int32_t *users, const int32_t *items, int64_t n, const int32_t *js,
                          int32_t num_ng, int32_t *triples, daisy_stream_t stream) {
     DAISY_CHECK_ARG(users && items && js && triples && n > 0 && num_ng > 0, "expand_triples: bad argument");
-    hipLaunchKernelGGL(k_expand_triples, dim3(grid_for(n * num_ng, kBlock)), dim3(kBlock), 0, S(stream),
+    hipLaunchKernelGGL(k_expand_triples, dim3(grid_for(n * num_ng, kBlock)), dim3(kBlock), 0, as_stream(stream),
                        users, items, n, js, (int)num_ng, triples);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -250,7 +249,7 @@ int daisy_resample_neg_per_interaction(const int64_t *indptr, const int32_t *csr
     DAISY_CHECK_ARG(indptr && csr_items && triples && n > 0 && item_num > 0,
                     "resample_neg_per_interaction: bad argument");
     DAISY_CHECK_ARG(epoch < kStreamPerm, "resample_neg_per_interaction: epoch out of range");
-    hipLaunchKernelGGL(k_resample_per_interaction, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, S(stream),
+    hipLaunchKernelGGL(k_resample_per_interaction, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, as_stream(stream),
                        indptr, csr_items, item_num, triples, n, seed, epoch | kStreamInteraction);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
@@ -266,7 +265,7 @@ int daisy_randperm(int64_t n, uint64_t seed, uint64_t epoch, int64_t *perm, void
     DAISY_CHECK_ARG(perm && workspace && n > 0, "randperm: bad argument");
     DAISY_CHECK_ARG(epoch < kStreamPerm, "randperm: epoch out of range");
     DAISY_CHECK_ARG(workspace_bytes >= daisy_randperm_workspace_bytes(n), "randperm: workspace too small");
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     char *w = (char *)workspace;
     uint64_t *kin = (uint64_t *)w;   w += align_up((size_t)n * 8);
     uint64_t *kout = (uint64_t *)w;  w += align_up((size_t)n * 8);
@@ -351,7 +350,7 @@ extern "C" int daisy_build_candidates(const int64_t *indptr_test, const int32_t 
                         n_users > 0 && item_num > 0 && cand_num > 0,
                     "build_candidates: bad argument");
     hipLaunchKernelGGL(daisy::k_build_candidates, dim3(daisy::grid_for(n_users * cand_num, daisy::kBlock)),
-                       dim3(daisy::kBlock), 0, reinterpret_cast<hipStream_t>(stream), indptr_test, items_test,
+                       dim3(daisy::kBlock), 0, as_stream(stream), indptr_test, items_test,
                        indptr_train, items_train, users, n_users, item_num, (int)cand_num, seed, out);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;

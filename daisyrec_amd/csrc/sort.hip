@@ -1,7 +1,7 @@
 // rocPRIM (AMD's native device primitives) wrappers.  Only index preparation
 // goes through these radix sorts (grouping a batch by user / by item, the
 // epoch permutation, argsort of candidate scores); the gather / dot / update
-// kernels of the hot path are hand written in bpr_train.hip.
+// kernels of the hot path are hand written (bpr_train.hip, bpr_staged.hip and the models' own files).
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -13,14 +13,23 @@ namespace daisy {
 // rocPRIM's default sends every sort of up to 1 M items to its merge sort, which ignores end_bit: ~18 launches of
 // ~6 us for the 524 288 13-bit keys of a NeuMF step, where Onesweep needs a histogram and two digit passes.
 // The id sorts here know their key width, so Onesweep takes over above 262 144 items (measured: merge sort still wins at 131 072 and below).
+constexpr unsigned kIdSortMergeLimit = 262144;
 using IdSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                rocprim::default_config, 262144>;
+                                                rocprim::default_config, kIdSortMergeLimit>;
 
 size_t sort_pairs_i32_temp_bytes(int64_t n) {
     size_t bytes = 0;
     (void)rocprim::radix_sort_pairs<IdSortConfig>(nullptr, bytes, (const int32_t *)nullptr, (int32_t *)nullptr,
                                     (const int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0, 32);
     return bytes;
+}
+
+// A context sized for sorts of up to n items also meets smaller ones, and the merge sort below the limit may ask for
+// more scratch than Onesweep does above it: the larger of the two regimes' largest requests.
+size_t sort_pairs_i32_temp_bytes_upto(int64_t n) {
+    const size_t at_n = sort_pairs_i32_temp_bytes(n);
+    const size_t at_limit = sort_pairs_i32_temp_bytes(n < (int64_t)kIdSortMergeLimit ? n : (int64_t)kIdSortMergeLimit);
+    return at_n > at_limit ? at_n : at_limit;
 }
 
 int sort_pairs_i32(void *temp, size_t temp_bytes, const int32_t *kin, int32_t *kout,

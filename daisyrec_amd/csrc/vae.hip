@@ -17,7 +17,7 @@
 // reparameterisation + KL gradients, the dense encoder layers, then dW0T from the kept entries only: the batch's
 // entries sorted by item (stable radix sort), every run summed in batch order by its head.  No float atomics.
 #include "common.h"
-#include "neumf_internal.h"
+#include "gemm.h"
 
 namespace daisy {
 
@@ -568,8 +568,7 @@ struct daisy_vae_ctx {
     int64_t b_off[2][DAISY_VAE_MAX_HIDDEN + 1];
     int64_t n_params;
     int maxw;                                   // widest hidden / latent layer
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
+    DeviceArena arena;
     int32_t *ent_item, *ent_row, *ent_idx, *kout, *vout, *row_len, *row_bad;
     float *ent_coef, *ent_val;
     int64_t *row_off;
@@ -582,8 +581,6 @@ struct daisy_vae_ctx {
 };
 
 namespace {
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the product of one Linear layer (or of its gradients): split-k to about kVaeTargetTiles workgroups, the slices summed
 // in order by k_vae_reduce together with the bias and the activation; a product that needs neither goes straight to C
@@ -766,8 +763,7 @@ int vae_step(daisy_vae_ctx *c, const float *W, float *g, const VaeBatch &vb, con
     const int d1 = c->enc[1];
     if (int rc = vae_colsum(c, G, B, d1, g + c->b_off[0][0], s)) return rc;
     if (E > 0) {
-        int bits = 1;
-        while (bits < 31 && (1ll << bits) <= I) ++bits;                  // ids 0 .. I (I: the padding sentinel)
+        const int bits = bits_for(I + 1);                                // ids 0 .. I (I: the padding sentinel)
         if (int rc = sort_pairs_i32(c->sort_tmp, c->sort_bytes, c->ent_item, c->kout, c->ent_idx, c->vout, E, bits, s)) return rc;
         const bool v4 = d1 % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0;      // (G: an arena slot, 256-byte aligned)
         hipLaunchKernelGGL(v4 ? k_vae_w0grad_v4 : k_vae_w0grad, dim3(grid_for(E, 1, kMaxGridSparse)), dim3(kBlock), 0, s, c->kout,
@@ -830,50 +826,20 @@ int daisy_vae_ctx_create(daisy_vae_ctx **out, int64_t max_batch, int64_t max_ent
     const int64_t Bm = max_batch, Em = max_entries > 0 ? max_entries : 1;
     c->ws_floats = (size_t)(kVaeTargetTiles + 64) * 128 * 128;      // split-k slices; column-sum chunks (>= one row of I)
     if (c->ws_floats < (size_t)item_num * 4) c->ws_floats = (size_t)item_num * 4;
-    c->sort_bytes = sort_pairs_i32_temp_bytes(Em);
-    const size_t merge_bytes = sort_pairs_i32_temp_bytes(Em < 262144 ? Em : 262144);
-    if (merge_bytes > c->sort_bytes) c->sort_bytes = merge_bytes;
-    size_t sizes[64];
-    void **slots[64];
-    int ns = 0;
-    auto add = [&](void **slot, size_t bytes) {
-        slots[ns] = slot;
-        sizes[ns++] = al(bytes);
-    };
-    add((void **)&c->ent_item, Em * 4);
-    add((void **)&c->ent_row, Em * 4);
-    add((void **)&c->ent_idx, Em * 4);
-    add((void **)&c->kout, Em * 4);
-    add((void **)&c->vout, Em * 4);
-    add((void **)&c->ent_coef, Em * 4);
-    add((void **)&c->ent_val, Em * 4);
-    add((void **)&c->row_len, Bm * 4);
-    add((void **)&c->row_bad, Bm * 4);
-    add((void **)&c->row_off, Bm * 8);
-    add((void **)&c->rsum, Bm * 8);
-    add((void **)&c->ce, Bm * 8);
-    add((void **)&c->kl, Bm * 8);
-    for (int l = 1; l <= n + 1; ++l) add((void **)&c->act[0][l], (size_t)Bm * c->enc[l] * 4);
-    for (int k = 0; k <= n; ++k) add((void **)&c->act[1][k], (size_t)Bm * c->dec[k] * 4);
-    add((void **)&c->eps, (size_t)Bm * c->dec[0] * 4);
-    add((void **)&c->logits, (size_t)Bm * item_num * 4);
-    add((void **)&c->G1, (size_t)Bm * maxw * 4);
-    add((void **)&c->G2, (size_t)Bm * maxw * 4);
-    add((void **)&c->ws, c->ws_floats * 4);
-    add(&c->sort_tmp, c->sort_bytes);
-    size_t total = 0;
-    for (int k = 0; k < ns; ++k) total += sizes[k];
-    hipError_t e = hipMalloc(&c->arena, total);
-    if (e != hipSuccess) {
+    c->sort_bytes = sort_pairs_i32_temp_bytes_upto(Em);
+    DeviceArena &a = c->arena;
+    a.add(&c->ent_item, Em * 4); a.add(&c->ent_row, Em * 4); a.add(&c->ent_idx, Em * 4); a.add(&c->kout, Em * 4);
+    a.add(&c->vout, Em * 4); a.add(&c->ent_coef, Em * 4); a.add(&c->ent_val, Em * 4);
+    a.add(&c->row_len, Bm * 4); a.add(&c->row_bad, Bm * 4);
+    a.add(&c->row_off, Bm * 8); a.add(&c->rsum, Bm * 8); a.add(&c->ce, Bm * 8); a.add(&c->kl, Bm * 8);
+    for (int l = 1; l <= n + 1; ++l) a.add(&c->act[0][l], (size_t)Bm * c->enc[l] * 4);
+    for (int k = 0; k <= n; ++k) a.add(&c->act[1][k], (size_t)Bm * c->dec[k] * 4);
+    a.add(&c->eps, (size_t)Bm * c->dec[0] * 4); a.add(&c->logits, (size_t)Bm * item_num * 4);
+    a.add(&c->G1, (size_t)Bm * maxw * 4); a.add(&c->G2, (size_t)Bm * maxw * 4);
+    a.add(&c->ws, c->ws_floats * 4); a.add(&c->sort_tmp, c->sort_bytes);
+    if (int rc = a.alloc("vae_ctx_create")) {
         delete c;
-        set_error("vae_ctx_create: hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
-        return DAISY_ERR_HIP;
-    }
-    c->arena_bytes = total;
-    char *q = static_cast<char *>(c->arena);
-    for (int k = 0; k < ns; ++k) {
-        *slots[k] = q;
-        q += sizes[k];
+        return rc;
     }
     *out = c;
     return DAISY_OK;
@@ -881,12 +847,12 @@ int daisy_vae_ctx_create(daisy_vae_ctx **out, int64_t max_batch, int64_t max_ent
 
 int daisy_vae_ctx_destroy(daisy_vae_ctx *ctx) {
     if (!ctx) return DAISY_OK;
-    if (ctx->arena) (void)hipFree(ctx->arena);
+    ctx->arena.release();
     delete ctx;
     return DAISY_OK;
 }
 
-size_t daisy_vae_ctx_bytes(const daisy_vae_ctx *ctx) { return ctx ? ctx->arena_bytes : 0; }
+size_t daisy_vae_ctx_bytes(const daisy_vae_ctx *ctx) { return ctx ? ctx->arena.bytes() : 0; }
 
 int64_t daisy_vae_param_count(const daisy_vae_ctx *ctx) { return ctx ? ctx->n_params : 0; }
 
@@ -898,7 +864,7 @@ int daisy_vae_step_grads(daisy_vae_ctx *ctx, const float *W, float *g, const int
     if (int rc = vae_check_batch(ctx, row_ptr, col, val, user_num, users, B, n_entries, dropout_p, "vae_step_grads")) return rc;
     DAISY_CHECK_ARG(anneal >= 0.f && anneal <= 1e30f, "vae_step_grads: anneal=%g", (double)anneal);
     const VaeBatch vb = vae_batch(ctx, row_ptr, col, val, user_num, users, B, n_entries, keep, train, dropout_p, seed);
-    return vae_step(ctx, W, g, vb, train ? eps : nullptr, anneal, stats, reinterpret_cast<hipStream_t>(stream));
+    return vae_step(ctx, W, g, vb, train ? eps : nullptr, anneal, stats, as_stream(stream));
 }
 
 int daisy_vae_fit_epoch(daisy_vae_ctx *ctx, float *W, float *g, const int64_t *row_ptr, const int32_t *col, const float *val,
@@ -908,9 +874,7 @@ int daisy_vae_fit_epoch(daisy_vae_ctx *ctx, float *W, float *g, const int64_t *r
                         double *stats, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && W && g && stats && entries && users && n > 0 && batch > 0 && step0 >= 0 && opt_step0 >= 0 && update0 >= 0,
                     "vae_fit_epoch: bad argument");
-    DAISY_CHECK_ARG(optimizer >= 0 && optimizer <= 3, "vae_fit_epoch: optimizer=%d (0 sgd, 1 adam, 2 adagrad, 3 rmsprop)", optimizer);
-    DAISY_CHECK_ARG(optimizer == 0 || state0, "vae_fit_epoch: optimizer %d needs its state", optimizer);
-    DAISY_CHECK_ARG(optimizer != 1 || state1, "vae_fit_epoch: Adam needs both moments");
+    if (int rc = dense_opt_check("vae_fit_epoch", optimizer, state0, state1)) return rc;
     DAISY_CHECK_ARG(anneal_cap >= 0.0 && anneal_cap <= 1e30, "vae_fit_epoch: anneal_cap=%g", anneal_cap);
     const int64_t nb = (n + batch - 1) / batch;
     for (int64_t k = 0; k < nb; ++k) {
@@ -918,7 +882,7 @@ int daisy_vae_fit_epoch(daisy_vae_ctx *ctx, float *W, float *g, const int64_t *r
         if (int rc = vae_check_batch(ctx, row_ptr, col, val, user_num, users + k * batch, B, entries[k], dropout_p, "vae_fit_epoch"))
             return rc;
     }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     const int64_t nf = ctx->n_params;
     int64_t t = opt_step0;
     for (int64_t k = 0; k < nb; ++k) {
@@ -933,12 +897,7 @@ int daisy_vae_fit_epoch(daisy_vae_ctx *ctx, float *W, float *g, const int64_t *r
                                       seed_hi | (uint64_t)(step0 + k + 1));
         if (int rc = vae_step(ctx, W, g, vb, nullptr, (float)an, stats, s)) return rc;
         ++t;
-        int rc;
-        if (optimizer == 0) rc = daisy_sgd_dense(W, g, nf, lr, stream);
-        else if (optimizer == 1) rc = daisy_adam_dense(W, g, state0, state1, nf, lr, 0.9f, 0.999f, 1e-8f, t, stream);
-        else if (optimizer == 2) rc = daisy_adagrad_dense(W, g, state0, nf, lr, 1e-10f, stream);
-        else rc = daisy_rmsprop_dense(W, g, state0, nf, lr, 0.99f, 1e-8f, stream);
-        if (rc) return rc;
+        if (int rc = dense_opt_step(optimizer, W, g, state0, state1, nf, lr, t, stream)) return rc;
     }
     return DAISY_OK;
 }
@@ -950,7 +909,7 @@ int daisy_vae_scores(daisy_vae_ctx *ctx, const float *W, const int64_t *row_ptr,
     DAISY_CHECK_ARG(ctx && W && out, "vae_scores: null argument");
     if (int rc = vae_check_batch(ctx, row_ptr, col, val, user_num, users, B, n_entries, dropout_p, "vae_scores")) return rc;
     DAISY_CHECK_ARG(!items || C >= 1, "vae_scores: C=%lld with candidates", (long long)C);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     const VaeBatch vb = vae_batch(ctx, row_ptr, col, val, user_num, users, B, n_entries, keep, train, dropout_p, seed);
     if (int rc = vae_forward(ctx, W, vb, train ? eps : nullptr, s)) return rc;      // (user ids: checked by the caller)
     const int n = ctx->n_hidden, wl = ctx->dec[n];

@@ -335,7 +335,8 @@ int daisy_bpr_item_sgd_apply(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, 
                              daisy_stream_t stream);
 
 /* torch.optim.Adam.step (defaults, AbstractRecommender.py:54), DENSE like the
- * reference: every element moves every step.  g is zeroed.  step is 1-based. */
+ * reference: every element moves every step.  g is zeroed.  step is 1-based.
+ * (The four dense optimisers - this one, Adagrad, RMSprop, SGD - are csrc/dense_opt.hip.) */
 int daisy_adam_dense(float *W, float *g, float *m, float *v, int64_t n, float lr, float beta1,
                      float beta2, float eps, int64_t step, daisy_stream_t stream);
 
@@ -578,7 +579,7 @@ int daisy_neumf_fit_epoch(daisy_neumf_ctx *ctx, const daisy_neumf_params *params
                           float gamma, float reg_1, float reg_2, float dropout_p, uint64_t seed_hi, int64_t step0,
                           int32_t optimizer, float lr, float *W, float *g, float *state0, float *state1, int64_t n_flat,
                           double *stats, daisy_stream_t stream);
-/* optim.SGD step on one dense tensor: W -= lr*g; g = 0   (AbstractRecommender.py:56) */
+/* optim.SGD step on one dense tensor: W -= lr*g; g = 0   (AbstractRecommender.py:56; csrc/dense_opt.hip) */
 int daisy_sgd_dense(float *W, float *g, int64_t n, float lr, daisy_stream_t stream);
 /* the argsort / top-k tail of every rank(): scores f32[B,C] (+ candidate ids i64[B,C]) -> ids of the
  * topk best per row, stable descending like torch.argsort(descending=True); workspace as
@@ -589,7 +590,8 @@ int daisy_topk_from_scores(const float *scores, const int64_t *cands, int64_t B,
                            daisy_stream_t stream);
 int daisy_full_topk_from_scores(const float *scores, int64_t item_num, int32_t topk, int64_t *out_ids,
                                 void *workspace, size_t workspace_bytes, daisy_stream_t stream);
-/* C[M,N] = A[M,K] * B[N,K]^T on the fp32 MFMA tile kernel the MLP tower uses (test / bench hook) */
+/* The MFMA products of csrc/gemm.hip (NeuMF's tower and Multi-VAE's layers run on them) as entry points of their own:
+ * C[M,N] = A[M,K] * B[N,K]^T on the fp32 MFMA tile kernel the MLP tower uses (test / bench hook) */
 int daisy_gemm_nt_f32(const float *A, const float *B, float *C, int64_t M, int32_t N, int32_t K,
                       daisy_stream_t stream);
 /* C[M,N] = A[M,K] * B[N,K]^T with all three matrices stored as bf16 (fp32 accumulate, round to nearest even): the

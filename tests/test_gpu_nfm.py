@@ -240,6 +240,55 @@ def test_fit_epoch_loss_is_the_sum_of_the_step_losses():
     assert first == losses[0]
 
 
+@pytest.mark.parametrize("opt", ["sgd", "adam", "adagrad", "rmsprop"])
+def test_fit_epoch_equals_step_grads_plus_the_dense_optimiser(opt):
+    """daisy_nfm_fit_epoch against daisy_nfm_step_grads + daisy_{sgd,adam,adagrad,rmsprop}_dense issued step by step:
+    the flat parameters, the optimiser state and the BatchNorm buffers bit for bit.  20 triples in batches of 7 (three
+    steps, the last one partial), starting at optimiser step 5 and dropout step 9: a loop that fed Adam the dropout
+    counter, or the count from 0, would show in the bias correction."""
+    from daisyrec_amd import ops
+    from daisyrec_amd import _native as N
+    rng = np.random.default_rng(13)
+    U, I, d, L, n, B, seed, t0, s0 = 11, 13, 8, 1, 20, 7, 5, 5, 9
+    tri = [_i32(rng.integers(0, m, n)) for m in (U, I, I)]
+
+    def run(native):
+        model = _random_model(np.random.default_rng(4), U, I, d, L, dropout=0.0, reg_1=1e-3, reg_2=1e-3, lr=0.01)
+        p = model._params()
+        init = _np(model._flat).copy()
+        gflat = torch.zeros_like(model._flat)
+        g = model._grad_table(gflat)
+        loss_id = ops.LOSS_IDS[model.loss_type.upper()]
+        optim = ops.DenseOptimizer(opt, model.lr)
+        optim.t = t0
+        ctx = model._ctx(B)
+        try:
+            if native:
+                steps = ctx.fit_epoch(p, g, model._bn(), *tri, B, optim, model._flat, gflat, loss_id, model.reg_1, model.reg_2,
+                                      dropout=0.0, seed_hi=seed << 32, step0=s0)
+            else:
+                steps = 0
+                for b0 in range(0, n, B):
+                    steps += 1
+                    ctx.step_grads(p, g, model._bn(), *(t[b0:b0 + B] for t in tri), loss_id, model.reg_1, model.reg_2,
+                                   dropout=0.0, seed=(seed << 32) | (s0 + steps))
+                    optim.next_step()
+                    optim.step(model._flat, gflat)
+            loss = float(ctx.stats[N.NFST_LOSS_SUM].cpu())
+        finally:
+            ctx.close()
+        bufs = [_np(x).copy() for row in model._bn() for x in row]
+        return steps, optim.t, loss, _np(model._flat).copy(), [_np(x).copy() for x in optim.state_for(model._flat)], bufs, init
+
+    a, b = run(True), run(False)
+    assert a[0] == b[0] == 3 and a[1] == b[1] == t0 + 3
+    assert a[2] == b[2] and np.isfinite(a[2]) and a[2] > 0
+    assert np.array_equal(a[3].view(np.uint8), b[3].view(np.uint8)) and not np.array_equal(a[3], a[6])
+    assert len(a[4]) == len(b[4]) == {"sgd": 0, "adam": 2, "adagrad": 1, "rmsprop": 1}[opt]
+    assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a[4], b[4]))
+    assert len(a[5]) == 3 * (L + 1) and all(np.array_equal(x, y) for x, y in zip(a[5], b[5]))
+
+
 def test_one_row_batch_with_batch_norm_raises():
     from daisyrec_amd.utils.dataset import BasicDataset, get_dataloader
     rng = np.random.default_rng(2)

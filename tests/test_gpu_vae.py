@@ -419,6 +419,65 @@ def test_fit_epoch_equals_the_step_replay(ml):
     assert a.update == 2 * nb and a._steps == 2 * nb
 
 
+@pytest.mark.parametrize("opt", ["sgd", "adam", "adagrad", "rmsprop"])
+def test_fit_epoch_equals_step_grads_plus_the_dense_optimiser(opt):
+    """daisy_vae_fit_epoch against daisy_vae_step_grads + daisy_{sgd,adam,adagrad,rmsprop}_dense issued step by step:
+    the flat parameters and the optimiser state bit for bit.  12 users x 40 items in batches of 5 (three steps, the last
+    one of 2 users), hidden [8], latent 4, the anneal still rising; the optimiser starts at step 5 and the noise at step
+    9, so a loop that fed Adam the wrong counter would show in the bias correction."""
+    from daisyrec_amd import ops
+    from daisyrec_amd import _native as N
+    from daisyrec_amd.model import VAECF
+    rng = np.random.default_rng(3)
+    U, I, Lh, B, t0, s0, u0 = 12, 40, 9, 5, 5, 9, 2
+    hid = np.zeros((U, Lh), dtype=np.int64)
+    hval = np.zeros((U, Lh), dtype=np.float32)
+    for u in range(U):
+        k = int(rng.integers(3, Lh + 1))
+        hid[u, :k] = np.sort(rng.choice(np.arange(1, I), size=k, replace=False))
+        hval[u, :k] = 1.0
+    users = torch.as_tensor(rng.permutation(U), dtype=torch.int64)
+    cap, total = 0.9, 8
+
+    def run(native):
+        torch.manual_seed(2)
+        m = VAECF(vae_config(user_num=U, item_num=I, mlp_hidden_size=[8], latent_dim=4, dropout=0.0, lr=0.01, seed=7,
+                             anneal_cap=cap, total_anneal_steps=total, history_item_id=torch.from_numpy(hid),
+                             history_item_value=torch.from_numpy(hval)))
+        W = m._params()
+        init = W.cpu().numpy().copy()
+        csr, lens = m._csr()
+        entries = [int(x.sum()) for x in torch.split(lens[users], B)]
+        g = torch.zeros_like(W)
+        optim = ops.DenseOptimizer(opt, m.lr)
+        optim.t = t0
+        seed_hi = (int(m.seed) & 0xFFFFFFFF) << 32
+        ctx = ops.VaeContext(B, max(entries), I, m.layers, m.lat_dim)
+        try:
+            if native:
+                steps = ctx.fit_epoch(W, g, csr, users.cuda(), B, entries, optim, 0.0, cap, total, u0, seed_hi=seed_hi, step0=s0)
+                loss = float(ctx.stats[N.VST_LOSS_SUM].cpu())
+            else:
+                steps, loss = 0, 0.0
+                for k, us in enumerate(torch.split(users, B)):
+                    steps += 1
+                    ctx.step_grads(W, g, csr, us.cuda(), entries[k], train=True, dropout=0.0,
+                                   anneal=f32(VO.anneal_at(u0 + steps, cap, total)), seed=seed_hi | (s0 + steps))
+                    loss += float(ctx.stats[N.VST_LOSS])
+                    optim.next_step()
+                    optim.step(W, g)
+        finally:
+            ctx.close()
+        return steps, optim.t, loss, W.cpu().numpy().copy(), [x.cpu().numpy().copy() for x in optim.state_for(W)], init
+
+    a, b = run(True), run(False)
+    assert a[0] == b[0] == 3 and a[1] == b[1] == t0 + 3
+    assert a[2] == b[2] and np.isfinite(a[2]) and a[2] > 0
+    assert np.array_equal(a[3].view(np.uint8), b[3].view(np.uint8)) and not np.array_equal(a[3], a[5])
+    assert len(a[4]) == len(b[4]) == {"sgd": 0, "adam": 2, "adagrad": 1, "rmsprop": 1}[opt]
+    assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a[4], b[4]))
+
+
 def test_second_fit_carries_anneal_and_restarts_adam(ml):
     """two fits = one replay of both whose Adam restarts at the boundary (a fresh optimiser per fit) while the update
     counter and the noise keys carry on; a replay that keeps the first fit's Adam state gives other bits"""

@@ -39,6 +39,36 @@ def test_argument_errors_do_not_need_a_gpu():
     assert N.lib.daisy_mf_rank_workspace_bytes(0, 10) == 0
 
 
+def test_fit_epoch_entries_reject_a_bad_optimiser_without_a_gpu():
+    """The three library-issued epoch loops share one optimiser check (csrc/dense_opt.hip): an unknown optimiser, Adam
+    without its second moment and Adagrad without its state are DAISY_ERR_ARG with the entry point's own name in front,
+    before the context or any HIP call is touched (the pointers here are dummies nobody reads)."""
+    from daisyrec_amd import _native as N
+    buf = ctypes.create_string_buffer(256)
+    d = ctypes.addressof(buf)
+    ref = ctypes.byref
+    pn, pf, bn = N.NeumfParams(), N.NfmParams(), N.NfmBnState()
+    calls = {
+        "neumf": lambda opt, s0, s1: N.lib.daisy_neumf_fit_epoch(d, ref(pn), ref(pn), d, d, d, 8, 4, 0, 1e-10, 0.0, 0.0, 0.0,
+                                                                 0, 0, opt, 0.01, d, d, s0, s1, 16, d, None),
+        "nfm": lambda opt, s0, s1: N.lib.daisy_nfm_fit_epoch(d, ref(pf), ref(pf), ref(bn), d, d, d, 8, 4, 0, 1e-10, 0.0, 0.0,
+                                                             0.0, 0, 0, 0, opt, 0.01, d, d, s0, s1, 16, d, None),
+        "vae": lambda opt, s0, s1: N.lib.daisy_vae_fit_epoch(d, d, d, d, d, d, 4, d, 8, 4, d, 0.0, 0.2, 0, 0, 0, 0, 0, opt,
+                                                             0.01, s0, s1, d, None),
+    }
+    cases = [(4, d, d, "optimizer=4 (0 sgd, 1 adam, 2 adagrad, 3 rmsprop)"),
+             (-1, d, d, "optimizer=-1 (0 sgd, 1 adam, 2 adagrad, 3 rmsprop)"),
+             (1, d, None, "Adam needs both moments"),
+             (1, None, d, "optimizer 1 needs its state"),
+             (2, None, None, "optimizer 2 needs its state"),
+             (3, None, None, "optimizer 3 needs its state")]
+    for name, call in calls.items():
+        for opt, s0, s1, text in cases:
+            rc = call(opt, s0, s1)
+            assert rc == N.DAISY_ERR_ARG, (name, opt, rc)
+            assert N.last_error() == f"{name}_fit_epoch: {text}", (name, opt, N.last_error())
+
+
 def test_product_path_never_imports_oracle():
     """oracle/ is test infrastructure: nothing under daisyrec_amd/ may reference it."""
     pkg = os.path.join(ROOT, "daisyrec_amd")
