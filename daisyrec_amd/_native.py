@@ -74,6 +74,8 @@ _nb = C.POINTER(NfmBnState)
 VAE_MAX_HIDDEN, VAE_KEEP_STREAM, VAE_EPS_STREAM = 8, 0x400, 0x401
 VST_LOSS, VST_LOSS_SUM, VST_CE, VST_KL, VST_NONFINITE, VST_BAD_ROWS = range(6)
 VAE_STATS_LEN = 8
+SLIM_LDS_ITEMS, SLIM_MAX_TOPK = 9984, 1024
+SLIM_PATHS = {"auto": 0, "lds": 1, "global": 2}
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
@@ -195,6 +197,13 @@ SIGNATURES = {
     "daisy_vae_fit_epoch": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _f32, C.c_double, _i64, _i64, _u64,
                                       _i64, _i64, _i32, _f32, _p, _p, _p, _p]),
     "daisy_vae_scores": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _f32, _u64, _p, _p]),
+    "daisy_slim_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "daisy_slim_gram_fits": (C.c_int, [_i64, _i64, _i64, _sz]),
+    "daisy_slim_gram": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    "daisy_slim_cd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "daisy_slim_cd": (C.c_int, [_p, _i64, _i64, C.c_double, C.c_double, C.c_double, _i32, _i32, _i64, _i64, _p, _p, _p, _p,
+                                _p, _p, _i32, _p, _sz, _p]),
+    "daisy_slim_scores": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i32, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

@@ -48,6 +48,12 @@ def install(sampler=False, front_end=False):
     from .model.VAECFRecommender import VAECF
     ref_vae = importlib.import_module("daisy.model.VAECFRecommender")
     ref_vae.VAECF = VAECF
+    from .model.SLiMRecommender import SLiM
+    try:                                   # the reference module imports scipy and scikit-learn
+        ref_slim = importlib.import_module("daisy.model.SLiMRecommender")
+        ref_slim.SLiM = SLiM
+    except ImportError:
+        pass
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -7,3 +7,4 @@ from .NGCFRecommender import NGCF  # noqa: F401
 from .NFMRecommender import NFM  # noqa: F401
 from .Item2VecRecommender import Item2Vec  # noqa: F401
 from .VAECFRecommender import VAECF  # noqa: F401
+from .SLiMRecommender import SLiM  # noqa: F401

@@ -1331,3 +1331,125 @@ class VaeContext(_Native):
                                    _ptr(eps, torch.float32, "eps"), int(bool(train)), float(dropout),
                                    int(seed) & (2 ** 64 - 1), _ptr(out, torch.float32, "out"), _stream()))
         return out
+
+
+# ---- SLiM (csrc/slim.hip; SLiMRecommender.py) --------------------------------------------------------------------------
+def slim_csr(users, items, ratings, user_num, item_num):
+    """X of SLiM._convert_df (SLiMRecommender.py:148-157) as a CSR on the device of the inputs: (row_ptr int64 [U + 1],
+    col int32, val float32), items ascending within a row, duplicate (user, item) pairs summed in the order given (what
+    the COO -> CSC conversion does).  Built once per fit with torch ops (off the hot path); ids must be in range."""
+    users = torch.as_tensor(users).reshape(-1).to(torch.int64)
+    dev = users.device
+    items = torch.as_tensor(items).reshape(-1).to(dev, torch.int64)
+    vals = torch.as_tensor(ratings).reshape(-1).to(dev, torch.float64)
+    U, I = int(user_num), int(item_num)
+    key, order = torch.sort(users * I + items, stable=True)
+    vals = vals[order]
+    uniq, inverse, counts = torch.unique_consecutive(key, return_inverse=True, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    pos = torch.arange(key.numel(), device=dev, dtype=torch.int64) - start[inverse]
+    acc = torch.zeros(uniq.numel(), dtype=torch.float64, device=dev)
+    for r in range(int(counts.max()) if counts.numel() else 0):     # the r-th occurrence of every pair: distinct targets
+        sel = pos == r
+        acc[inverse[sel]] += vals[sel]
+    row = uniq // I
+    per_row = torch.bincount(row, minlength=U) if row.numel() else torch.zeros(U, dtype=torch.int64, device=dev)
+    row_ptr = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+    row_ptr[1:] = torch.cumsum(per_row, 0)
+    return row_ptr, (uniq % I).to(torch.int32).contiguous(), acc.to(torch.float32).contiguous()
+
+
+def _slim_csr_ptrs(csr):
+    row_ptr, col, val = csr
+    if col.numel() == 0:          # no interaction at all: the entry points still want two readable arrays
+        col, val = col.new_zeros(1), val.new_zeros(1)
+    return (_ptr(row_ptr, torch.int64, "row_ptr"), _ptr(col, torch.int32, "col"), _ptr(val, torch.float32, "val"),
+            row_ptr.numel() - 1)
+
+
+def slim_gram(csr, item_num, tile_rows=0, offered_bytes=None):
+    """G = X^T X, float32 [I, I] (daisy_slim_gram): user blocks of tile_rows rows (0: the default) through the fp32 MFMA
+    product, added in block order.  offered_bytes: what G and the workspace may take together (default: the device's
+    free memory); a problem that does not fit is refused before anything is allocated."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    I = int(item_num)
+    dev = csr[0].device
+    if offered_bytes is None:
+        with torch.cuda.device(dev):
+            offered_bytes = torch.cuda.mem_get_info()[0]
+    check(lib.daisy_slim_gram_fits(U, I, int(tile_rows), int(offered_bytes)))
+    ws = _ws(lib.daisy_slim_gram_workspace_bytes(U, I, int(tile_rows)), dev)
+    G = torch.empty(I, I, dtype=torch.float32, device=dev)
+    check(lib.daisy_slim_gram(rp, cp, vp, U, I, _ptr(G, torch.float32, "G"), _ptr(ws, torch.uint8, "ws"), ws.numel(),
+                              _stream()))
+    return G
+
+
+def slim_fit(G, n_users, alpha, l1_ratio, topk, tol=1e-4, max_iter=100, col0=0, ncols=None, path="auto", moves=None):
+    """The elastic nets of the columns [col0, col0 + ncols) of G (daisy_slim_cd) -> (count int32 [ncols], rows int32
+    [ncols, topk], vals float32 [ncols, topk], sweeps int32 [ncols], gap float64 [ncols]); the kept pairs of a column by
+    descending value, then ascending row.  moves (int64 [ncols], optional): gets every column's count of coordinate updates
+    that changed a value (each read one row of G)."""
+    I = int(G.shape[0])
+    if G.dim() != 2 or G.shape[1] != I:
+        raise ValueError(f"G: expected a square matrix, got {tuple(G.shape)}")
+    ncols = I - int(col0) if ncols is None else int(ncols)
+    dev, k = G.device, int(topk)
+    count = torch.empty(max(ncols, 0), dtype=torch.int32, device=dev)
+    rows = torch.empty(max(ncols, 0), max(k, 0), dtype=torch.int32, device=dev)
+    vals = torch.empty(max(ncols, 0), max(k, 0), dtype=torch.float32, device=dev)
+    sweeps = torch.empty(max(ncols, 0), dtype=torch.int32, device=dev)
+    gap = torch.empty(max(ncols, 0), dtype=torch.float64, device=dev)
+    p = N.SLIM_PATHS[path]
+    ws = _ws(lib.daisy_slim_cd_workspace_bytes(I, max(ncols, 0), p), dev)
+    check(lib.daisy_slim_cd(_ptr(G, torch.float32, "G"), I, int(n_users), float(alpha), float(l1_ratio), float(tol),
+                            int(max_iter), k, int(col0), ncols, _ptr(count, torch.int32, "count"),
+                            _ptr(rows, torch.int32, "rows"), _ptr(vals, torch.float32, "vals"),
+                            _ptr(sweeps, torch.int32, "sweeps"), _ptr(gap, torch.float64, "gap"),
+                            _ptr(moves, torch.int64, "moves"), p,
+                            _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return count, rows, vals, sweeps, gap
+
+
+def slim_columns(count, rows, vals, item_num):
+    """The kept pairs of slim_fit for ALL item_num columns as the column form daisy_slim_scores reads: (w_ptr int64
+    [I + 1], w_row int32 ascending within a column, w_val float32; never empty: one unused slot when nothing is kept).
+    Torch ops, once per fit."""
+    ncols, k = rows.shape
+    if ncols != int(item_num):
+        raise ValueError(f"slim_columns: {ncols} columns given, item_num={item_num} (the slabs of every column, concatenated)")
+    dev = rows.device
+    taken = torch.arange(k, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)
+    colid = torch.arange(ncols, device=dev, dtype=torch.int64).unsqueeze(1).expand(ncols, k)[taken]
+    r, v = rows[taken].to(torch.int64), vals[taken]
+    order = torch.argsort(colid * max(ncols, 1) + r)
+    w_ptr = torch.zeros(ncols + 1, dtype=torch.int64, device=dev)
+    w_ptr[1:] = torch.cumsum(count.to(torch.int64), 0)
+    w_row, w_val = r[order].to(torch.int32).contiguous(), v[order].contiguous()
+    if w_row.numel() == 0:
+        w_row, w_val = w_row.new_zeros(1), w_val.new_zeros(1)
+    return w_ptr, w_row, w_val
+
+
+def slim_scores(csr, W, item_num, users, items=None, path="auto"):
+    """Rows of A_tilde = X W for users [B] (daisy_slim_scores): float32 [B, C] at the candidates items [B, C] (int64), or
+    [B, item_num].  W: slim_columns' triple."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    w_ptr, w_row, w_val = W
+    I = int(item_num)
+    users = users.to(torch.int64).contiguous()
+    B = users.numel()
+    if items is not None:
+        items = items.to(torch.int64).contiguous()
+        if items.dim() != 2 or items.shape[0] != B:
+            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
+        Cn = int(items.shape[1])
+        out = torch.empty(B, Cn, dtype=torch.float32, device=users.device)
+    else:
+        Cn = 0
+        out = torch.empty(B, I, dtype=torch.float32, device=users.device)
+    check(lib.daisy_slim_scores(rp, cp, vp, U, I, _ptr(w_ptr, torch.int64, "w_ptr"), _ptr(w_row, torch.int32, "w_row"),
+                                _ptr(w_val, torch.float32, "w_val"), _ptr(users, torch.int64, "users"), B,
+                                _ptr(items, torch.int64, "items"), Cn, _ptr(out, torch.float32, "out"), N.SLIM_PATHS[path],
+                                _stream()))
+    return out

@@ -862,6 +862,56 @@ int daisy_vae_scores(daisy_vae_ctx *ctx, const float *W, const int64_t *row_ptr,
                      const uint8_t *keep, const float *eps, int32_t train, float dropout_p, uint64_t seed, float *out,
                      daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * SLiM (daisy/model/SLiMRecommender.py, SLiM): one non-negative elastic net per item column over the Gram matrix,
+ * truncated to the topk largest coefficients, scored by a sparse product (csrc/slim.hip).
+ * X is the [user_num, item_num] rating matrix as a CSR (row_ptr int64 [user_num + 1], col int32 ascending within a
+ * row, val float32, duplicate (user, item) pairs already summed).
+ * ---------------------------------------------------------------------- */
+#define DAISY_SLIM_LDS_ITEMS 9984   /* item_num up to which the descent state (w, H: 16 bytes per item) lives in LDS */
+#define DAISY_SLIM_MAX_TOPK 1024
+enum { DAISY_SLIM_PATH_AUTO = 0, DAISY_SLIM_PATH_LDS = 1, DAISY_SLIM_PATH_GLOBAL = 2 };
+/* bytes of daisy_slim_gram's workspace: one [item_num, item_num] fp32 partial product and the [tile_rows, item_num]
+ * fp32 tile the user blocks are densified into (tile_rows <= 0: the default, at most 1024 rows; otherwise rounded up to a
+ * multiple of 16).  0 for item_num < 1. */
+size_t daisy_slim_gram_workspace_bytes(int64_t user_num, int64_t item_num, int64_t tile_rows);
+/* DAISY_ERR_ARG, with the three figures in the message, when G (item_num^2 * 4 bytes) plus that workspace does not fit
+ * the offered_bytes the caller can give them; no HIP call. */
+int daisy_slim_gram_fits(int64_t user_num, int64_t item_num, int64_t tile_rows, size_t offered_bytes);
+/* G = X^T X, fp32 [item_num, item_num] (SLiMRecommender.py:84: ElasticNet(precompute=True) forms it in every fit):
+ * blocks of users are densified into the tile, tile^T tile runs on the fp32 MFMA product and the blocks' products are
+ * added in block order: no atomics, reproducible run to run, exact while every partial sum is an integer below 2^24.
+ * The tile's rows follow from workspace_bytes (as daisy_slim_gram_workspace_bytes lays it out; at least 16 rows). */
+int daisy_slim_gram(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t user_num, int64_t item_num,
+                    float *G, void *workspace, size_t workspace_bytes, daisy_stream_t stream);
+/* bytes of daisy_slim_cd's workspace (column counter, diagonal of G and, on the global path, w and H of every
+ * workgroup) for ncols columns; path: DAISY_SLIM_PATH_* (AUTO: LDS up to DAISY_SLIM_LDS_ITEMS items).  0 on bad arguments. */
+size_t daisy_slim_cd_workspace_bytes(int64_t item_num, int64_t ncols, int32_t path);
+/* SLiMRecommender.py:73-107 for the columns [col0, col0 + ncols): per column j the cyclic coordinate descent of
+ *   min 1/2 w'Qw - q'w + a |w|_1 + 1/2 b |w|^2 over w >= 0,  Q = G without row / column j, q = G[:, j] (q[j] = 0),
+ *   a = alpha * l1_ratio * n_users, b = alpha * (1 - l1_ratio) * n_users
+ * (sklearn's enet_coordinate_descent_gram with positive=True, selection='cyclic'): w, H = Qw and the duality gap in
+ * fp64, G widened on load and never written; stops when gap < tol * G[j, j], after max_iter sweeps at the latest.  Then
+ * the truncation of :86-107: the min(nz - 1, topk) largest coefficients (ties: lower row), rounded to fp32.
+ * Outputs: kept_count int32 [ncols]; kept_row int32 / kept_val float32 [ncols, topk], descending value then ascending
+ * row, unused slots (-1, 0); sweeps int32 [ncols] (0 for a column with G[j, j] == 0); gap float64 [ncols]; moves int64
+ * [ncols] or NULL: the coordinate updates that changed a value, each of which read one row of G (a measurement hook).
+ * One workgroup per column, fed from an atomic column counter; the result does not depend on which workgroup ran a
+ * column.  alpha > 0, 0 <= l1_ratio <= 1, tol >= 0, max_iter >= 1, 1 <= topk <= DAISY_SLIM_MAX_TOPK. */
+int daisy_slim_cd(const float *G, int64_t item_num, int64_t n_users, double alpha, double l1_ratio, double tol,
+                  int32_t max_iter, int32_t topk, int64_t col0, int64_t ncols, int32_t *kept_count, int32_t *kept_row,
+                  float *kept_val, int32_t *sweeps, double *gap, int64_t *moves, int32_t path, void *workspace,
+                  size_t workspace_bytes, daisy_stream_t stream);
+/* rows of A_tilde = X W (SLiMRecommender.py:123-127, 135, 144) for the users[B] (int64): out[B][C] at the candidates
+ * items[B][C] (int64), or out[B][item_num] when items == NULL.  W is the truncated matrix by column (w_ptr int64
+ * [item_num + 1], w_row int32 ascending within a column, w_val float32).  A score is the fp64 sum over its column's
+ * entries in ascending row of X[u, row] * val, rounded once to fp32.  One workgroup per user: the user's row of X is
+ * scattered into LDS (path LDS; AUTO up to 32768 items) or looked up by binary search in the CSR row (path GLOBAL).
+ * A user or item id out of range scores 0. */
+int daisy_slim_scores(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t user_num, int64_t item_num,
+                      const int64_t *w_ptr, const int32_t *w_row, const float *w_val, const int64_t *users, int64_t B,
+                      const int64_t *items, int64_t C, float *out, int32_t path, daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Drive the reference's own `run_examples/test.py` with the HIP path behind its model classes
 (INTEGRATION.md §1): nothing in daisyRec is edited; `daisyrec_amd.dropin.install()` rebinds
-`MF` / `FM` / `NeuMF` / `LightGCN` / `Item2Vec` (and, with --native-sampler, `BasicNegtiveSampler`).
+`MF` / `FM` / `NeuMF` / `LightGCN` / `Item2Vec` / `SLiM` ... (and, with --native-sampler, `BasicNegtiveSampler`).
 
     python tools/run_daisy_example.py --daisy /path/to/daisyRec -- --algo_name mf --epochs 5
 
