@@ -20,10 +20,9 @@
 //
 // Measured on MI355X (profiles/r01_probe_*): random 256-B row gathers / plain
 // stores run at 5-8 TB/s, fp32 global atomics at 0.3 TB/s.  So every scatter is
-// organised around OWNERSHIP instead of atomics: an EPOCH PLAN (radix sorts, once
-// per epoch) lays the epoch out batch by batch, each batch grouped by user, plus
-// a per-batch list of item entries sorted by item; the item gradient is then a
-// segmented reduction over that list.
+// organised around OWNERSHIP instead of atomics: the epoch plan (epoch_plan.hip)
+// hands over every batch grouped by user, plus a list of its item entries sorted
+// by item; the item gradient is then a segmented reduction over that list.
 //
 // HBM/L2 view: a d=64 row is 256 B = 16 lanes x float4, one coalesced request
 // per quarter wave; four rows are in flight per wave instruction.
@@ -34,126 +33,13 @@
 
 namespace daisy {
 
-
-// ---------------------------------------------------------------------------
-// epoch plan kernels
-// ---------------------------------------------------------------------------
-// order_mode: 0 identity, 1 explicit permutation (perm[p] = triple at position p), 2 Feistel
-// ids outside [0,U) x [0,I) x [0,I) (point-wise rows: the third column is a label) raise *bad and are
-// replaced by 0, so that no later kernel reads or writes outside the tables (daisy_epoch_plan_validate
-// reports it; the reference raises IndexError in nn.Embedding, MFRecommender.py:64-65)
-template <class KeyT>
-__global__ void k_plan_keys(const int32_t *__restrict__ triples, const int64_t *__restrict__ perm,
-                            int order_mode, FeistelKey fk, int64_t n, int64_t start, int64_t B,
-                            int32_t user_base, int ubits, int64_t U, int64_t I, int pointwise,
-                            int *__restrict__ bad, KeyT *__restrict__ key, uint64_t *__restrict__ val,
-                            int64_t perm_limit) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-         e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t t, p;
-        if (order_mode == 1) { p = e; t = perm[e]; }
-        else if (order_mode == 2) { t = e; p = (int64_t)feistel_position((uint64_t)e, (uint64_t)n, fk); }
-        else { t = e; p = e; }
-        if (order_mode == 1 && (t < 0 || t >= perm_limit)) { atomicOr(bad, 2); t = 0; }     // (rows the entry may name)
-        const int32_t *row = triples + 3 * (t + start);
-        int64_t uu = (int64_t)row[0] - user_base;
-        int32_t ri = row[1], rj = row[2];
-        if (uu < 0 || uu >= U || ri < 0 || ri >= I || (!pointwise && (rj < 0 || rj >= I))) {
-            atomicOr(bad, 1);
-            uu = 0; ri = 0; rj = 0;
-        }
-        key[e] = (KeyT)(((uint64_t)(p / B) << ubits) | (uint64_t)uu);
-        val[e] = ((uint64_t)(uint32_t)rj << 32) | (uint32_t)ri;      // (j, i)
-    }
-}
-
-// from the user-grouped samples: the two item entries of every sample
-template <class KeyT>
-__global__ void k_plan_entries(const KeyT *__restrict__ skey, const uint64_t *__restrict__ sval,
-                               int64_t n, int64_t B, int ibits, uint32_t umask, int pointwise,
-                               KeyT *__restrict__ ekey, uint64_t *__restrict__ eval) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n;
-         p += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t k = (uint64_t)(p / B);
-        const uint32_t s = (uint32_t)(p - (int64_t)k * B);
-        const uint32_t uu = (uint32_t)skey[p] & umask;
-        const uint64_t ij = sval[p];
-        ekey[2 * p] = (KeyT)((k << (ibits + 1)) | ((uint64_t)(uint32_t)ij << 1));
-        eval[2 * p] = ((uint64_t)uu << 32) | s;
-        const uint32_t jn = pointwise ? (uint32_t)ij : (uint32_t)(ij >> 32);
-        ekey[2 * p + 1] = (KeyT)((k << (ibits + 1)) | ((uint64_t)jn << 1) | 1u);
-        eval[2 * p + 1] = ((uint64_t)uu << 32) | (s | kNegBit);
-    }
-}
-
-// 64-bit sort keys -> the 32-bit id arrays the step kernels read
-__global__ void k_narrow_keys(const uint64_t *__restrict__ in, int64_t n, uint64_t mask,
-                              uint32_t *__restrict__ out) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-         e += (int64_t)gridDim.x * blockDim.x)
-        out[e] = (uint32_t)(in[e] & mask);
-}
-
-// runs of equal entry keys -> per-batch run offsets (lower bound of batch k's first key) and
-// the narrowed run keys (item << 1 | neg)
-template <class KeyT>
-__global__ void k_run_finish(const KeyT *__restrict__ full_key, const uint32_t *__restrict__ run_total,
-                             int64_t nb, int ibits1, uint32_t *__restrict__ run_key,
-                             int32_t *__restrict__ run_off) {
-    const int64_t R = *run_total;
-    const uint64_t imask = ((uint64_t)1 << ibits1) - 1;
-    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t m = tid; m < R; m += stride) run_key[m] = (uint32_t)((uint64_t)full_key[m] & imask);
-    for (int64_t k = tid; k <= nb; k += stride) {
-        const uint64_t target = (uint64_t)k << ibits1;
-        int64_t lo = 0, hi = R;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((uint64_t)full_key[mid] < target) lo = mid + 1;
-            else hi = mid;
-        }
-        run_off[k] = (int32_t)lo;
-    }
-}
-
+// daisy_bpr_set_batch: three id columns -> the rows a one-batch plan is built from
 __global__ void k_pack_triples(const int32_t *__restrict__ u, const int32_t *__restrict__ i,
                                const int32_t *__restrict__ j, int64_t B, int32_t *__restrict__ out) {
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < B;
          s += (int64_t)gridDim.x * blockDim.x) {
         out[3 * s] = u[s]; out[3 * s + 1] = i[s]; out[3 * s + 2] = j[s];
     }
-}
-
-__global__ void k_unpack_batch(BatchView v, int32_t *__restrict__ u, int32_t *__restrict__ i,
-                               int32_t *__restrict__ j, int32_t *__restrict__ ent_item,
-                               uint32_t *__restrict__ ent_s, int32_t *__restrict__ ent_u) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < 2 * v.B;
-         e += (int64_t)gridDim.x * blockDim.x) {
-        if (e < v.B) {
-            u[e] = (int32_t)(v.ukey[e] & v.umask);
-            i[e] = v.ij[e].x;
-            j[e] = v.ij[e].y;
-        }
-        if (ent_item) ent_item[e] = (int32_t)((v.ekey[e] & v.imask) >> 1);
-        if (ent_s) ent_s[e] = v.esu[e].x;
-        if (ent_u) ent_u[e] = (int32_t)v.esu[e].y;
-    }
-}
-
-// out[k] = position of triple ids[k] (a rank's rows of a multi-GPU fit)
-__global__ void k_feistel_at(const int64_t *__restrict__ ids, int64_t m, int64_t n, FeistelKey fk,
-                             int64_t *__restrict__ out) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t t = ids[e];
-        out[e] = (t >= 0 && t < n) ? (int64_t)feistel_position((uint64_t)t, (uint64_t)n, fk) : -1;
-    }
-}
-
-__global__ void k_feistel_perm(int64_t n, FeistelKey fk, int64_t *__restrict__ out) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-         e += (int64_t)gridDim.x * blockDim.x)
-        out[e] = (int64_t)feistel_position((uint64_t)e, (uint64_t)n, fk);
 }
 
 // ---------------------------------------------------------------------------
@@ -1099,183 +985,6 @@ __global__ __launch_bounds__(kBlock) void k_adam_flush(AdamTable T, int64_t rows
     }
 }
 
-// ---------------------------------------------------------------------------
-// plan construction (host side)
-// ---------------------------------------------------------------------------
-static int plan_alloc(daisy_epoch_plan **out, int64_t max_triples, int64_t U, int64_t I) {
-    daisy_epoch_plan *p = new daisy_epoch_plan();      // (all zero: no device memory yet, each layout allocates at its first build)
-    p->max_triples = max_triples; p->U = U; p->I = I;
-    *out = p;
-    return DAISY_OK;
-}
-
-// buffers of the sorted layout (kind 0)
-static int plan_need_sorted(daisy_epoch_plan *p) {
-    if (p->arena.bytes()) return DAISY_OK;
-    const int64_t max_triples = p->max_triples;
-    const size_t n2 = 2 * (size_t)max_triples;
-    const size_t ta = sort_pairs_u32_u64_temp_bytes(n2), tb = sort_pairs_u64_u64_temp_bytes(n2);
-    const size_t tc = rle_u32_temp_bytes(n2), td = rle_u64_temp_bytes(n2);
-    p->temp_bytes = ta > tb ? ta : tb;
-    if (tc > p->temp_bytes) p->temp_bytes = tc;
-    if (td > p->temp_bytes) p->temp_bytes = td;
-    DeviceArena &a = p->arena;
-    a.add(&p->k32[0], n2 * 4); a.add(&p->k32[1], n2 * 4);
-    a.add(&p->v64[0], n2 * 8); a.add(&p->v64[1], n2 * 8);
-    a.add(&p->ukey, (size_t)max_triples * 4);   // sorted sample keys survive the entry sort
-    a.add(&p->uval, (size_t)max_triples * 8);
-    a.add(&p->run_key, n2 * 4); a.add(&p->run_cnt, n2 * 4); a.add(&p->run_off, ((size_t)max_triples + 2) * 4);
-    a.add(&p->run_total, 256);
-    a.add(&p->temp, p->temp_bytes);
-    if (int rc = a.alloc("epoch_plan_build")) {
-        a.release();
-        return rc;
-    }
-    p->k64[0] = p->k64[1] = nullptr;                // allocated on demand (rare: > 32 key bits)
-    p->bad = (int *)((char *)p->run_total + 64);
-    p->ekey = nullptr; p->eval = nullptr;
-    p->umask = p->imask = 0;
-    return DAISY_OK;
-}
-
-static int plan_free(daisy_epoch_plan *p) {
-    const hipError_t e = p->arena.release() ? hipSuccess : hipGetLastError();
-    for (int k = 0; k < 2; ++k)
-        if (p->k64[k]) (void)hipFree(p->k64[k]);
-    if (p->parena) (void)hipFree(p->parena);
-    if (p->parena2) (void)hipFree(p->parena2);
-    if (p->d_off) (void)hipFree(p->d_off);
-    free(p->h_off);
-    delete p;
-    if (e != hipSuccess) {
-        set_error("epoch_plan_destroy: hipFree failed: %s", hipGetErrorString(e));
-        return DAISY_ERR_HIP;
-    }
-    return DAISY_OK;
-}
-
-static int plan_need_k64(daisy_epoch_plan *p) {
-    for (int k = 0; k < 2; ++k) {
-        if (!p->k64[k]) {
-            hipError_t e = hipMalloc((void **)&p->k64[k], 2 * (size_t)p->max_triples * 8);
-            if (e != hipSuccess) {
-                set_error("epoch_plan_build: hipMalloc of 64-bit key buffers failed: %s", hipGetErrorString(e));
-                return DAISY_ERR_HIP;
-            }
-        }
-    }
-    return DAISY_OK;
-}
-
-// flags: DAISY_PLAN_TRIPLES_USER_SORTED -> the samples only need a stable partition by batch
-// perm_limit: rows of `triples` a permutation entry may name (n for a permutation of the n rows; the whole array when the
-// entries SELECT n of its rows: daisy_bpr_set_batch_from_triples - whose range check compared against n until round 4, so
-// that a selection naming a row >= its own length was refused)
-static int plan_build(daisy_epoch_plan *p, const int32_t *triples, int64_t n, int64_t start,
-                      const int64_t *perm, int order_mode, uint64_t seed, uint64_t epoch,
-                      int64_t batch_size, int32_t user_base, int32_t flags, hipStream_t s, int64_t perm_limit = -1) {
-    if (perm_limit < 0) perm_limit = n;
-    const int ubits = bits_for(p->U), ibits = bits_for(p->I);
-    const int64_t nb = (n + batch_size - 1) / batch_size;
-    const int bbits = (nb > 1) ? bits_for(nb) : 0;
-    const uint32_t umask = (uint32_t)(((uint64_t)1 << ubits) - 1);
-    const int ibits1 = ibits + 1;                    // item << 1 | negative-slot bit
-    const uint32_t imask = (uint32_t)(((uint64_t)1 << ibits1) - 1);
-    const bool wide = (ubits + bbits > 32) || (ibits1 + bbits > 32);
-    const bool presorted = (flags & DAISY_PLAN_TRIPLES_USER_SORTED) && order_mode != DAISY_ORDER_PERM;
-    const int pointwise = (flags & DAISY_PLAN_POINTWISE) ? 1 : 0;
-    int rc = plan_need_sorted(p);
-    if (rc) return rc;
-    const int s_begin = presorted ? ubits : 0;      // user bits ride along unsorted
-    FeistelKey fk = make_feistel_key((uint64_t)n, seed, epoch);
-    const int g1 = grid_for(n, kBlock), g2 = grid_for(2 * n, kBlock);
-    DAISY_HIP(hipMemsetAsync(p->bad, 0, sizeof(int), s));
-    if (!wide) {
-        hipLaunchKernelGGL((k_plan_keys<uint32_t>), dim3(g1), dim3(kBlock), 0, s, triples, perm,
-                           order_mode, fk, n, start, batch_size, user_base, ubits, p->U, p->I, pointwise, p->bad,
-                           p->k32[0], p->v64[0], perm_limit);
-        DAISY_LAUNCH_CHECK();
-        if (ubits + bbits > s_begin) {
-            rc = sort_pairs_u32_u64(p->temp, p->temp_bytes, p->k32[0], p->ukey, p->v64[0], p->uval, n,
-                                    s_begin, ubits + bbits, s);
-            if (rc) return rc;
-        } else {   // one batch of user-sorted triples: already in plan order
-            DAISY_HIP(hipMemcpyAsync(p->ukey, p->k32[0], n * 4, hipMemcpyDeviceToDevice, s));
-            DAISY_HIP(hipMemcpyAsync(p->uval, p->v64[0], n * 8, hipMemcpyDeviceToDevice, s));
-        }
-        hipLaunchKernelGGL((k_plan_entries<uint32_t>), dim3(g1), dim3(kBlock), 0, s, p->ukey, p->uval,
-                           n, batch_size, ibits, umask, pointwise, p->k32[0], p->v64[0]);
-        DAISY_LAUNCH_CHECK();
-        rc = sort_pairs_u32_u64(p->temp, p->temp_bytes, p->k32[0], p->k32[1], p->v64[0], p->v64[1], 2 * n,
-                                0, ibits1 + bbits, s);
-        if (rc) return rc;
-        // runs of equal (batch, item, slot) keys: the distinct items of every batch + their counts
-        rc = rle_u32(p->temp, p->temp_bytes, p->k32[1], 2 * n, p->k32[0], p->run_cnt, p->run_total, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL((k_run_finish<uint32_t>), dim3(g2), dim3(kBlock), 0, s, p->k32[0], p->run_total,
-                           nb, ibits1, p->run_key, p->run_off);
-        DAISY_LAUNCH_CHECK();
-        p->umask = umask;
-        p->imask = imask;
-    } else {
-        if ((rc = plan_need_k64(p))) return rc;
-        hipLaunchKernelGGL((k_plan_keys<uint64_t>), dim3(g1), dim3(kBlock), 0, s, triples, perm,
-                           order_mode, fk, n, start, batch_size, user_base, ubits, p->U, p->I, pointwise, p->bad,
-                           p->k64[0], p->v64[0], perm_limit);
-        DAISY_LAUNCH_CHECK();
-        rc = sort_pairs_u64_u64(p->temp, p->temp_bytes, p->k64[0], p->k64[1], p->v64[0], p->uval, n,
-                                s_begin, ubits + bbits, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_narrow_keys, dim3(g1), dim3(kBlock), 0, s, p->k64[1], n, (uint64_t)umask,
-                           p->ukey);
-        DAISY_LAUNCH_CHECK();
-        hipLaunchKernelGGL((k_plan_entries<uint64_t>), dim3(g1), dim3(kBlock), 0, s, p->k64[1], p->uval,
-                           n, batch_size, ibits, 0xFFFFFFFFu & umask, pointwise, p->k64[0], p->v64[0]);
-        DAISY_LAUNCH_CHECK();
-        rc = sort_pairs_u64_u64(p->temp, p->temp_bytes, p->k64[0], p->k64[1], p->v64[0], p->v64[1], 2 * n,
-                                0, ibits1 + bbits, s);
-        if (rc) return rc;
-        rc = rle_u64(p->temp, p->temp_bytes, p->k64[1], 2 * n, p->k64[0], p->run_cnt, p->run_total, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL((k_run_finish<uint64_t>), dim3(g2), dim3(kBlock), 0, s, p->k64[0], p->run_total,
-                           nb, ibits1, p->run_key, p->run_off);
-        DAISY_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_narrow_keys, dim3(g2), dim3(kBlock), 0, s, p->k64[1], 2 * n, (uint64_t)imask,
-                           p->k32[1]);
-        DAISY_LAUNCH_CHECK();
-        p->umask = 0xFFFFFFFFu;
-        p->imask = 0xFFFFFFFFu;
-    }
-    p->ekey = p->k32[1];
-    p->eval = p->v64[1];
-    free(p->h_off); p->h_off = nullptr; p->h_off_cap = 0;          // (a plan that held a rank's share before)
-    if (p->d_off) { (void)hipFree(p->d_off); p->d_off = nullptr; }
-    p->n = n; p->batch_size = batch_size; p->num_batches = nb; p->built = true;
-    p->build_gen = next_plan_build_id();
-    p->pointwise = pointwise;
-    p->kind = 0;
-    return DAISY_OK;
-}
-
-static BatchView plan_view(const daisy_epoch_plan *p, int64_t k) {
-    const int64_t lo = k * p->batch_size;
-    BatchView v;
-    v.B = (p->n - lo < p->batch_size) ? (p->n - lo) : p->batch_size;
-    v.ukey = p->ukey + lo;
-    v.ij = reinterpret_cast<const int2 *>(p->uval + lo);
-    v.ekey = p->ekey + 2 * lo;
-    v.esu = reinterpret_cast<const uint2 *>(p->eval + 2 * lo);
-    v.run_key = p->run_key;
-    v.run_cnt = p->run_cnt;
-    v.run_off = p->run_off + k;
-    v.umask = p->umask;
-    v.imask = p->imask;
-    v.pointwise = p->pointwise;
-    v.bu = v.bi = v.b0 = v.g_bu = v.g_bi = v.g_b0 = nullptr;
-    v.halt = nullptr;
-    return v;
-}
-
 int launch_reduce_partials(const double *partials, int nblocks, double *stats, bool finalize, float reg_1,
                            float reg_2, double *epoch_acc, double *step_loss, hipStream_t s) {
     if (finalize)
@@ -1286,19 +995,6 @@ int launch_reduce_partials(const double *partials, int nblocks, double *stats, b
                            0.f, (double *)nullptr, (double *)nullptr);
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
-}
-
-// the same batch as the staged step reads it (stage slot = grouped sample position)
-static StreamView stream_view_of(const BatchView &v) {
-    StreamView sv;
-    sv.s_rec = nullptr; sv.s_user = v.ukey; sv.s_ij = v.ij;
-    sv.e_key = v.ekey; sv.e_kstride = 1; sv.e_pos = reinterpret_cast<const uint32_t *>(v.esu); sv.e_stride = 2;
-    sv.umask = v.umask; sv.imask = v.imask; sv.pos_base = 0;
-    sv.B = v.B; sv.E = 2 * v.B;
-    sv.halt = nullptr;
-    sv.pointwise = v.pointwise;
-    sv.p_stream = 0;
-    return sv;
 }
 
 }  // namespace daisy
@@ -1365,106 +1061,11 @@ static void view_bias(daisy_bpr_ctx *ctx) {
 // =============================================================================
 extern "C" {
 
-int daisy_epoch_plan_create(daisy_epoch_plan **out, int64_t max_triples, int64_t user_num,
-                            int64_t item_num) {
-    DAISY_CHECK_ARG(out != nullptr, "epoch_plan_create: out is NULL");
-    DAISY_CHECK_ARG(max_triples > 0 && max_triples < ((int64_t)1 << 30),
-                    "epoch_plan_create: max_triples=%lld out of range", (long long)max_triples);
-    DAISY_CHECK_ARG(user_num > 0 && user_num <= INT32_MAX && item_num > 0 && item_num <= INT32_MAX,
-                    "epoch_plan_create: user_num/item_num out of int32 range");
-    return plan_alloc(out, max_triples, user_num, item_num);
-}
-
-int daisy_epoch_plan_destroy(daisy_epoch_plan *plan) {
-    if (!plan) return DAISY_OK;
-    return plan_free(plan);
-}
-
-size_t daisy_epoch_plan_bytes(const daisy_epoch_plan *plan) {
-    return plan ? plan->arena.bytes() + plan->parena_bytes : 0;
-}
-
-int64_t daisy_epoch_plan_num_batches(const daisy_epoch_plan *plan) {
-    return (plan && plan->built) ? plan->num_batches : 0;
-}
-
-int daisy_epoch_plan_build(daisy_epoch_plan *plan, const int32_t *triples, int64_t n_triples,
-                           const int64_t *perm, int32_t order_mode, uint64_t seed, uint64_t epoch,
-                           int64_t batch_size, int32_t user_base, int32_t flags,
-                           daisy_stream_t stream) {
-    DAISY_CHECK_ARG(plan && triples, "epoch_plan_build: NULL argument");
-    DAISY_CHECK_ARG(n_triples > 0 && n_triples <= plan->max_triples,
-                    "epoch_plan_build: n_triples=%lld not in 1..%lld", (long long)n_triples,
-                    (long long)plan->max_triples);
-    DAISY_CHECK_ARG(batch_size > 0, "epoch_plan_build: batch_size must be positive");
-    DAISY_CHECK_ARG(order_mode >= DAISY_ORDER_IDENTITY && order_mode <= DAISY_ORDER_FEISTEL,
-                    "epoch_plan_build: bad order_mode %d", order_mode);
-    DAISY_CHECK_ARG(order_mode != DAISY_ORDER_PERM || perm != nullptr,
-                    "epoch_plan_build: DAISY_ORDER_PERM needs perm");
-    return plan_build(plan, triples, n_triples, 0, perm, order_mode, seed, epoch, batch_size, user_base,
-                      flags, as_stream(stream));
-}
-
-static int report_bad_ids(const int *bad_dev, const char *who, int64_t U, int64_t I, hipStream_t s) {
-    int bad = 0;
-    DAISY_HIP(hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-    DAISY_HIP(hipStreamSynchronize(s));
-    if (bad & 2) { set_error("%s: index out of range in the epoch permutation", who); return DAISY_ERR_ARG; }
-    if (bad & 1) {
-        set_error("%s: index out of range in the batch: need 0 <= user - user_base < %lld and 0 <= item < %lld "
-                  "(the reference raises IndexError in nn.Embedding, MFRecommender.py:64-65)", who, (long long)U,
-                  (long long)I);
-        return DAISY_ERR_ARG;
-    }
-    return DAISY_OK;
-}
-
-int daisy_epoch_plan_validate(const daisy_epoch_plan *plan, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(plan != nullptr, "epoch_plan_validate: NULL plan");
-    if (!plan->built) { set_error("epoch_plan_validate: plan has not been built"); return DAISY_ERR_STATE; }
-    if (plan->kind == 1) return DAISY_OK;            // a train index is validated when it is created
-    return report_bad_ids(plan->bad, "epoch_plan_build", plan->U, plan->I, as_stream(stream));
-}
-
 int daisy_bpr_ctx_validate_batch(const daisy_bpr_ctx *ctx, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx != nullptr, "ctx_validate_batch: NULL context");
     if (!ctx->batch_set) { set_error("ctx_validate_batch: no batch set"); return DAISY_ERR_STATE; }
     if (!ctx->own_plan || !ctx->own_plan->built || ctx->v.ukey != ctx->own_plan->ukey) return DAISY_OK;   // from an epoch plan
-    return report_bad_ids(ctx->own_plan->bad, "set_batch", ctx->U, ctx->I, as_stream(stream));
-}
-
-int daisy_epoch_plan_read_batch(const daisy_epoch_plan *plan, int64_t k, int32_t *u, int32_t *i,
-                                int32_t *j, int32_t *ent_item, uint32_t *ent_s, int32_t *ent_u,
-                                int64_t *B_out_host, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(plan && u && i && j, "epoch_plan_read_batch: NULL argument");
-    if (!plan->built) { set_error("epoch_plan_read_batch: plan has not been built"); return DAISY_ERR_STATE; }
-    DAISY_CHECK_ARG(k >= 0 && k < plan->num_batches, "epoch_plan_read_batch: batch %lld not in 0..%lld",
-                    (long long)k, (long long)plan->num_batches);
-    if (plan->kind == 1) return plan_read_batch_partitioned(plan, k, u, i, j, ent_item, ent_s, ent_u, B_out_host, as_stream(stream));
-    const BatchView v = plan_view(plan, k);
-    hipLaunchKernelGGL(k_unpack_batch, dim3(grid_for(2 * v.B, kBlock)), dim3(kBlock), 0, as_stream(stream), v, u, i,
-                       j, ent_item, ent_s, ent_u);
-    DAISY_LAUNCH_CHECK();
-    if (B_out_host) *B_out_host = v.B;
-    return DAISY_OK;
-}
-
-int daisy_feistel_positions(int64_t n, uint64_t seed, uint64_t epoch, int64_t *out,
-                            daisy_stream_t stream) {
-    DAISY_CHECK_ARG(out && n > 0 && n <= ((int64_t)1 << 30), "feistel_positions: n must be in 1..2^30");
-    FeistelKey fk = make_feistel_key((uint64_t)n, seed, epoch);
-    hipLaunchKernelGGL(k_feistel_perm, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, as_stream(stream), n, fk, out);
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_feistel_positions_at(const int64_t *ids, int64_t n_ids, int64_t n, uint64_t seed, uint64_t epoch,
-                               int64_t *out, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(ids && out && n_ids > 0 && n > 0 && n <= ((int64_t)1 << 30), "feistel_positions_at: bad argument");
-    FeistelKey fk = make_feistel_key((uint64_t)n, seed, epoch);
-    hipLaunchKernelGGL(k_feistel_at, dim3(grid_for(n_ids, kBlock)), dim3(kBlock), 0, as_stream(stream), ids, n_ids, n, fk, out);
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
+    return plan_report_bad(ctx->own_plan, "set_batch", as_stream(stream));
 }
 
 int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int64_t user_num,
@@ -1547,7 +1148,7 @@ int daisy_bpr_ctx_destroy(daisy_bpr_ctx *ctx) {
 
 size_t daisy_bpr_ctx_scratch_bytes(const daisy_bpr_ctx *ctx) {
     if (!ctx) return 0;
-    return ctx->arena.bytes() + (ctx->own_plan ? ctx->own_plan->arena.bytes() : 0);
+    return ctx->arena.bytes() + (ctx->own_plan ? plan_bytes(ctx->own_plan) : 0);
 }
 
 static int ensure_own_plan(daisy_bpr_ctx *ctx) {

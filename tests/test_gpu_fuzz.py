@@ -1,9 +1,9 @@
 """Randomised differential test of the staged epoch (csrc/bpr_staged.hip) at the sizes between the unit cases and the
 bench: batches of 1 ... 200 000 samples, tables of 1 ... 80 000 rows, any factor count, uniform and Zipf ids (hot users
 and items: long runs, long segments, long edge chains), every loss, SGD and torch's Adam, the item pass's flavours and
-launch forms forced on and off - one epoch (up to ~3 batches, the last one partial) through the partitioned plan and
-daisy_bpr_fit_epoch_sgd / daisy_bpr_fit_epoch_adam against the oracle (MFRecommender.py:63-97,
-AbstractRecommender.py:119-126) on the batches the plan serves.
+launch forms forced on and off - one epoch (up to ~3 batches, the last one partial) through the partitioned plan
+(csrc/epoch_plan.hip) and daisy_bpr_fit_epoch_sgd / daisy_bpr_fit_epoch_adam against the oracle
+(MFRecommender.py:63-97, AbstractRecommender.py:119-126) on the batches the plan serves.
 
 Case k is a pure function of (DAISY_FUZZ_SEED, k): a failure names its case and reproduces alone.  DAISY_FUZZ_CASES
 (default 36) widens the campaign: the round's long run is recorded in profiles/r05_fuzz.txt."""

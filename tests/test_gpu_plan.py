@@ -182,3 +182,109 @@ def test_plan_user_sorted_fast_path_and_wide_keys():
     P0 = (rng.standard_normal((Us, d)) * 0.1).astype(np.float32)
     Q0 = (rng.standard_normal((Is, d)) * 0.1).astype(np.float32)
     plan.close()
+
+
+def _read(plan, k, B):
+    return [t.cpu().numpy() for t in plan.read_batch(k, B)]
+
+
+def _check_partitioned(plan, tri, pos, B):
+    """every batch of a partitioned plan against the oracle (the comparison of test_partitioned_plan_bit_exact)"""
+    n = len(tri)
+    nb = (n + B - 1) // B
+    assert plan.num_batches == nb
+    samples, spos, ekey, epos = O.partitioned_plan(tri, pos, B)
+    for k in range(nb):
+        lo, hi = k * B, min((k + 1) * B, n)
+        u, i, j, ei, es, _ = _read(plan, k, B)
+        assert np.array_equal(np.stack([u, i, j], 1).astype(np.int64), samples[lo:hi]), k
+        assert np.array_equal(np.sort(spos[lo:hi]), np.arange(lo, hi))
+        assert np.array_equal(ei.astype(np.int64), ekey[2 * lo:2 * hi] >> 1), k
+        want_s = ((epos[2 * lo:2 * hi] - lo) | ((ekey[2 * lo:2 * hi] & 1) << 31)).astype(np.uint32)
+        assert np.array_equal(es.astype(np.uint32), want_s), k
+
+
+def test_one_plan_object_through_every_layout_in_turn():
+    """One plan object rebuilt in the sorted layout, the partitioned layout with one and with two LSD passes, as a
+    rank's share and back: each layout allocates its memory once, at the first build that needs it, and a rebuild in
+    another layout neither frees nor disturbs it (nbytes: 256-byte slots, the second record set = two arrays of 16 n
+    bytes)."""
+    from daisyrec_amd import ops
+    n, U, I = 3000, 300, 200
+    tri = _triples(n, U, I, 11)
+    t_dev = torch.from_numpy(tri).to(DEV)
+    plan = ops.EpochPlan(n, U, I)
+    index = ops.TrainIndex(t_dev, U, I)
+    pos = O.feistel_positions(n, 31, 2)
+    # 1. sorted layout
+    plan.build(t_dev, 64, order="identity")
+    nb = plan.num_batches
+    assert nb == 47
+    for k in (0, nb - 1):
+        _check_batch(plan, k, 64, tri[k * 64:(k + 1) * 64], U)
+    first = _read(plan, 0, 64)
+    S = plan.nbytes
+    # 2. partitioned, one pass
+    plan.build_indexed(index, 64, order="feistel", seed=31, epoch=2)
+    _check_partitioned(plan, tri, pos, 64)
+    P0 = plan.nbytes - S
+    assert P0 > 0
+    # 3. partitioned, two LSD passes: the second record set
+    plan.build_indexed(index, 10, order="feistel", seed=31, epoch=2)
+    assert plan.num_batches == 300
+    _check_partitioned(plan, tri, pos, 10)
+    assert plan.nbytes == S + P0 + 96256
+    # 4. a rank's share: every third row, at its position in the same epoch order
+    held = np.ascontiguousarray(tri[::3])
+    hpos = pos[::3]
+    sub = ops.TrainIndex(torch.from_numpy(held).to(DEV), U, I)
+    plan.build_positions(sub, torch.from_numpy(hpos.astype(np.int64)).to(DEV), n, 64)
+    assert plan.num_batches == 47
+    rows = [plan.batch_rows(k) for k in range(47)]
+    assert sum(rows) == 1000
+    key = lambda a: a[np.lexsort((a[:, 2], a[:, 1], a[:, 0]))]
+    for k in range(47):
+        want = held[(hpos >= 64 * k) & (hpos < 64 * k + 64)]
+        assert rows[k] == len(want)
+        if rows[k]:
+            u, i, j, *_ = _read(plan, k, 64)
+            assert np.array_equal(key(np.stack([u, i, j], 1)), key(want)), k
+    # 5. the whole epoch again: the offsets of the share are dropped
+    plan.build_indexed(index, 64, order="identity")
+    assert [plan.batch_rows(k) for k in range(47)] == [64] * 46 + [56]
+    # 6. the sorted layout again: its buffers are as the first build left them
+    plan.build(t_dev, 64, order="identity")
+    for a, b in zip(_read(plan, 0, 64), first):
+        assert np.array_equal(a, b)
+    assert plan.nbytes == S + P0 + 96256
+    sub.close()
+    index.close()
+    plan.close()
+
+
+def test_index_bytes_follow_the_input_order():
+    """A user-sorted array is indexed in place (the index keeps its two entry arrays: 2 x 8192 bytes at n = 1000); any
+    other order adds the CSR copy (12 n -> 12032) and the row map (4 n -> 4096).  Both index the same rows: served in
+    the same order they give the same plan, element for element.  (Epoch positions refer to the CALLER's rows, so the
+    identity order of the shuffled array is another epoch: it is held against the oracle, and the permutation that
+    serves the shuffled rows in the sorted array's order against the sorted array's plan.)"""
+    from daisyrec_amd import ops
+    n, U, I, B = 1000, 40, 30, 128
+    shuffled = _triples(n, U, I, 5)
+    csr = np.argsort(shuffled[:, 0], kind="stable")              # csr[p] = shuffled row at place p of the sorted array
+    ordered = np.ascontiguousarray(shuffled[csr])
+    ix_o = ops.TrainIndex(torch.from_numpy(ordered).to(DEV), U, I)
+    ix_s = ops.TrainIndex(torch.from_numpy(shuffled).to(DEV), U, I)
+    assert ix_o.nbytes == 16384
+    assert ix_s.nbytes == 32512
+    plan_o, plan_s = ops.EpochPlan(n, U, I), ops.EpochPlan(n, U, I)
+    plan_o.build_indexed(ix_o, B, order="identity")
+    plan_s.build_indexed(ix_s, B, order="identity")
+    _check_partitioned(plan_o, ordered, np.arange(n), B)
+    _check_partitioned(plan_s, shuffled, np.arange(n), B)
+    plan_s.build_indexed(ix_s, B, order="perm", perm=torch.from_numpy(csr.astype(np.int64)).to(DEV))
+    for k in range(plan_o.num_batches):
+        for a, b in zip(_read(plan_o, k, B), _read(plan_s, k, B)):
+            assert np.array_equal(a, b), k
+    for x in (plan_o, plan_s, ix_o, ix_s):
+        x.close()

@@ -1,4 +1,4 @@
-"""The partitioned epoch plan and the staged step (csrc/bpr_staged.hip): index work bit-exact against
+"""The partitioned epoch plan (csrc/epoch_plan.hip) and the staged step (csrc/bpr_staged.hip): index work bit-exact against
 the oracle's restatement, the step against oracle.mf_sgd_step (MFRecommender.py:63-97 + SGD) on the
 same batches, the phase form against the single call, bitwise reproducibility, id validation."""
 import numpy as np
