@@ -429,7 +429,7 @@ def test_neumf_fp32_first_layer_through_the_tables(loss, B, L, d, monkeypatch):
 
 @pytest.mark.parametrize("loss,B,level,U,I", [(0, 2048, 2, 300, 200), (3, 5000, 0, 950, 1200), (0, 4096, 0, 61, 9000), (2, 2112, 2, 40, 30)])
 def test_neumf_rows_grouped_by_a_counting_pass_equal_the_radix_sorts(loss, B, level, U, I, monkeypatch):
-    """Round 6: the step's rows are grouped by user and by item with one stable counting pass per side (csrc/neumf.hip:
+    """Round 6: the step's rows are grouped by user and by item with one stable counting pass per side (csrc/neumf_scatter.hip:
     k_cs_count / k_cs_prefix / k_cs_base / k_cs_scatter) instead of two radix sorts.  Stable = rows of one table row stay in
     ascending order = the very permutation the sorts produce, so every gradient must come out BIT FOR BIT the same with
     DAISY_NMF_COUNTING=0 (the sorts): pairwise and point-wise steps, both precisions, hot rows (40 users in 4 224 rows),
@@ -693,9 +693,9 @@ def test_neumf_argument_errors():
 @pytest.mark.parametrize("level", [0, 2])
 def test_neumf_step_is_bitwise_reproducible(level):
     """Hot users and items (every table row hit hundreds of times per step): the embedding gradients are
-    segmented reductions on a single owner per row, so two runs give identical bits (the fp32-atomics kernel
-    kept behind DAISY_NMF_SCATTER_OWNER=0 does not), and they agree with the atomic kernel's sums to round-off
-    - checked through the oracle KATs of this file, which run on the owner kernels by default.
+    segmented reductions on a single owner per row, so two runs give identical bits (fp32 atomics, which the first
+    version of the scatter used, do not), and the sums agree with the fp64 oracle's to round-off - checked through the oracle
+    KATs of this file, which run on the owner kernels.
     Round 3: the reductions over the batch rows that used fp32 atomics - the split-K slices of the MLP weight
     gradients (8 slices here), the bias column sums, the predict layer's gradient - now add per-workgroup partial
     sums in a fixed order (k_reduce_slices), so EVERY gradient of the step is bitwise repeatable."""
@@ -775,3 +775,60 @@ def test_neumf_first_layer_through_the_tables(loss, B, monkeypatch):
         cos = float((gf[k] * g32[k]).sum() / (np.linalg.norm(gf[k]) * n32 + 1e-30))
         assert ef < 0.25 and cos > 0.97, (k, ef, ep, cos)     # (against the FP32 mode: bf16's own distance from it; the tight
         assert ef < 2.5 * ep + 0.03, (k, ef, ep)             # check is test_neumf_bf16_step_against_the_bf16_oracle above)
+
+
+# (level, d, L, U, I, max_rows, [(call, B or pairs, dropout)]): the calls one context serves, and the path each of them takes
+REUSE_SEQUENCES = {
+    "fp32": (0, 24, 2, 60, 50, 8400, [("step", 256, 0.0),        # the one-launch mid kernel + the scanning scatter
+                                       ("step", 4200, 0.0),       # first layer through the tables, owner chain, counting pass
+                                       ("scores", 500, 0.0),      # eval forward
+                                       ("step", 4200, 0.3),       # plain layered path, counting pass
+                                       ("step", 256, 0.0)]),      # mid + scan again
+    "bf16": (2, 64, 3, 40, 30, 4224, [("step", 256, 0.0),         # fused tower, radix-sort owner chain
+                                       ("step", 100, 0.0),        # 200 rows, not whole tiles: level 1, plain + scanning scatter
+                                       ("step", 2112, 0.0),       # tower + counting pass
+                                       ("step", 256, 0.0)]),      # tower + radix sorts again
+}
+
+
+@pytest.mark.parametrize("name", sorted(REUSE_SEQUENCES))
+def test_neumf_context_reused_across_paths(name, monkeypatch):
+    """One context serves a sequence of calls that take different paths (REUSE_SEQUENCES: the paths follow from neumf_path and
+    neumf_scatter at the default settings).  Every call's loss and every gradient - the scores of the eval call - must equal
+    BIT FOR BIT what a fresh context of the same max_rows (the workspace size feeds the split-K slice length, hence the
+    summation order) produces for that call alone: nothing a call decides or leaves behind - its path, the table products,
+    the count and row-sum tables the scatter keeps all-zero between calls - may reach the next one."""
+    from daisyrec_amd import ops
+    for var in ("DAISY_NMF_MID", "DAISY_NMF_FACT", "DAISY_NMF_TOWER", "DAISY_NMF_COUNTING", "DAISY_NMF_SCATTER_SMALL"):
+        monkeypatch.delenv(var, raising=False)
+    level, d, L, U, I, max_rows, calls = REUSE_SEQUENCES[name]
+    rng = np.random.default_rng(3 + d)
+    shapes = _tower_shapes(U, I, d, L)
+    p = _dev({k: (rng.standard_normal(s) * 0.1).astype(np.float32) for k, s in shapes.items()})
+    batches = [[torch.as_tensor(rng.integers(0, m, n).astype(np.int32)).to(DEV) for m in (U, I, I)] for _, n, _ in calls]
+
+    def context():
+        ctx = ops.NeumfContext(max_rows, d, L, U, I)
+        ctx.set_precision(level)
+        return ctx
+
+    def call(ctx, k):
+        kind, _, pdrop = calls[k]
+        u, i, j = batches[k]
+        if kind == "scores":
+            return {"scores": ctx.scores(p, u.long(), i.long()).cpu().numpy()}
+        grads = {key: torch.zeros_like(v) for key, v in p.items()}
+        ctx.step_grads(p, grads, u, i, j, 0, 1e-3, 1e-3, dropout=pdrop, seed=99)
+        return {"loss": ctx.stats[11].cpu().numpy(), **{key: v.cpu().numpy() for key, v in grads.items()}}
+
+    shared = context()
+    for k in range(len(calls)):
+        got = call(shared, k)
+        fresh = context()
+        want = call(fresh, k)
+        fresh.close()
+        for key in want:
+            assert np.array_equal(got[key], want[key]), (name, k, calls[k], key)
+        if calls[k][0] == "step":
+            assert np.isfinite(want["loss"]) and all(np.abs(want[key]).max() > 0 for key in ("uG", "iM", "W1", "Wp")), (name, k)
+    shared.close()
