@@ -76,6 +76,7 @@ VST_LOSS, VST_LOSS_SUM, VST_CE, VST_KL, VST_NONFINITE, VST_BAD_ROWS = range(6)
 VAE_STATS_LEN = 8
 SLIM_LDS_ITEMS, SLIM_MAX_TOPK = 9984, 1024
 SLIM_PATHS = {"auto": 0, "lds": 1, "global": 2}
+PSVD_MAX_C, PSVD_CONVERGED, PSVD_NOT_CONVERGED = 256, 0, 1
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
@@ -204,6 +205,15 @@ SIGNATURES = {
     "daisy_slim_cd": (C.c_int, [_p, _i64, _i64, C.c_double, C.c_double, C.c_double, _i32, _i32, _i64, _i64, _p, _p, _p, _p,
                                 _p, _p, _i32, _p, _sz, _p]),
     "daisy_slim_scores": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i32, _p]),
+    "daisy_psvd_spmm": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _p, _p]),
+    "daisy_psvd_gram_block_rows": (_i64, [_i64, _i64]),
+    "daisy_psvd_gram_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "daisy_psvd_gram": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _sz, _p]),
+    "daisy_psvd_chol": (C.c_int, [_p, _i32, _i64, _p, _p, _p, _p]),
+    "daisy_psvd_gemm": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p]),
+    "daisy_psvd_jacobi_workspace_bytes": (_sz, [_i32]),
+    "daisy_psvd_jacobi": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p]),
+    "daisy_psvd_rank": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

@@ -54,6 +54,12 @@ def install(sampler=False, front_end=False):
         ref_slim.SLiM = SLiM
     except ImportError:
         pass
+    from .model.PureSVDRecommender import PureSVD
+    try:                                   # the reference module imports scipy and scikit-learn
+        ref_psvd = importlib.import_module("daisy.model.PureSVDRecommender")
+        ref_psvd.PureSVD = PureSVD
+    except ImportError:
+        pass
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

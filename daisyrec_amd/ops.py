@@ -1453,3 +1453,135 @@ def slim_scores(csr, W, item_num, users, items=None, path="auto"):
                                 _ptr(items, torch.int64, "items"), Cn, _ptr(out, torch.float32, "out"), N.SLIM_PATHS[path],
                                 _stream()))
     return out
+
+
+# ---- PureSVD (csrc/puresvd.hip; PureSVDRecommender.py) --------------------------------------------------------
+def _f64(t, name, dim=2):
+    if not isinstance(t, torch.Tensor) or t.dim() != dim:
+        raise TypeError(f"{name}: expected a {dim}-D torch.Tensor")
+    return _ptr(t, torch.float64, name)
+
+
+def psvd_spmm(csr, n_cols, X):
+    """Y [n_rows, c] = A X, float64 (daisy_psvd_spmm): A the CSR triple of slim_csr ([n_rows, n_cols]), X float64
+    [n_cols, c]; a row's non-zeros are accumulated in stored order."""
+    rp, cp, vp, n_rows = _slim_csr_ptrs(csr)
+    xp = _f64(X, "X")
+    if X.shape[0] != int(n_cols):
+        raise ValueError(f"X: expected [{int(n_cols)}, c], got {tuple(X.shape)}")
+    c = int(X.shape[1])
+    Y = torch.empty(n_rows, c, dtype=torch.float64, device=X.device)
+    check(lib.daisy_psvd_spmm(rp, cp, vp, n_rows, int(n_cols), xp, c, _ptr(Y, torch.float64, "Y"), _stream()))
+    return Y
+
+
+def psvd_gram(Y, block_rows=0):
+    """G [c, c] = Y^T Y, float64 (daisy_psvd_gram): blocks of block_rows rows (0: the default) on the fp64 MFMA, their
+    partial products added in block order."""
+    yp = _f64(Y, "Y")
+    n, c = int(Y.shape[0]), int(Y.shape[1])
+    ws = _ws(lib.daisy_psvd_gram_workspace_bytes(n, c, int(block_rows)), Y.device)
+    G = torch.empty(c, c, dtype=torch.float64, device=Y.device)
+    check(lib.daisy_psvd_gram(yp, n, c, _ptr(G, torch.float64, "G"), int(block_rows), _ptr(ws, torch.uint8, "ws"), ws.numel(),
+                              _stream()))
+    return G
+
+
+def psvd_chol(G, n):
+    """(R, Rinv, dropped) of daisy_psvd_chol: the upper R with R^T R = G that drops dependent columns (pivot not
+    > 64 n eps G_jj), the inverse of R restricted to the kept columns, and the dropped count as an int32 device tensor."""
+    gp = _f64(G, "G")
+    c = int(G.shape[0])
+    if G.shape[1] != c:
+        raise ValueError(f"G: expected a square matrix, got {tuple(G.shape)}")
+    R, Rinv = torch.empty_like(G), torch.empty_like(G)
+    dropped = torch.zeros(1, dtype=torch.int32, device=G.device)
+    check(lib.daisy_psvd_chol(gp, c, int(n), _ptr(R, torch.float64, "R"), _ptr(Rinv, torch.float64, "Rinv"),
+                              _ptr(dropped, torch.int32, "dropped"), _stream()))
+    return R, Rinv, dropped
+
+
+def psvd_gemm(Y, T):
+    """Y [n, c] T [c, c2] -> float64 [n, c2] on the fp64 MFMA (daisy_psvd_gemm)."""
+    yp, tp = _f64(Y, "Y"), _f64(T, "T")
+    n, c, c2 = int(Y.shape[0]), int(Y.shape[1]), int(T.shape[1])
+    if T.shape[0] != c:
+        raise ValueError(f"T: expected [{c}, c2], got {tuple(T.shape)}")
+    out = torch.empty(n, c2, dtype=torch.float64, device=Y.device)
+    check(lib.daisy_psvd_gemm(yp, tp, _ptr(out, torch.float64, "out"), n, c, c2, _stream()))
+    return out
+
+
+def psvd_orthonormalize(Y, block_rows=0):
+    """Cholesky-QR2 of Y [n, c] -> (Q, R, dropped): two rounds of Gram, Cholesky, Y R^-1; R = R2 R1.  For the kept columns
+    Q R = Y and Q^T Q = I; a dropped (dependent) column of Q is exactly zero.  dropped: int32 device tensor [1]."""
+    n = int(Y.shape[0])
+    R1, Ri1, _ = psvd_chol(psvd_gram(Y, block_rows), n)
+    Q1 = psvd_gemm(Y, Ri1)
+    R2, Ri2, dropped = psvd_chol(psvd_gram(Q1, block_rows), n)
+    return psvd_gemm(Q1, Ri2), psvd_gemm(R2, R1), dropped
+
+
+def psvd_jacobi(A, max_sweeps=60):
+    """One-sided Jacobi SVD of A [c, c] = U diag(s) V^T (daisy_psvd_jacobi) -> (U, s, V, info): s non-increasing, info an
+    int32 device tensor [status (N.PSVD_CONVERGED / N.PSVD_NOT_CONVERGED), sweeps]."""
+    ap = _f64(A, "A")
+    c = int(A.shape[0])
+    if A.shape[1] != c:
+        raise ValueError(f"A: expected a square matrix, got {tuple(A.shape)}")
+    U, V = torch.empty_like(A), torch.empty_like(A)
+    s = torch.empty(c, dtype=torch.float64, device=A.device)
+    info = torch.zeros(2, dtype=torch.int32, device=A.device)
+    ws = _ws(lib.daisy_psvd_jacobi_workspace_bytes(c), A.device)
+    check(lib.daisy_psvd_jacobi(ap, c, int(max_sweeps), _ptr(U, torch.float64, "U"), _ptr(s, torch.float64, "s"),
+                                _ptr(V, torch.float64, "V"), _ptr(info, torch.int32, "info"), _ptr(ws, torch.uint8, "ws"),
+                                ws.numel(), _stream()))
+    return U, s, V, info
+
+
+def psvd_fit(csr, csr_t, omega, n_iter, max_sweeps=60):
+    """randomized_svd's sequence for M [n, m] (csr: M, csr_t: M^T, both slim_csr triples) from the test matrix omega
+    float64 [m, r]: n_iter rounds of Q <- norm(M Q), Q <- norm(M^T Q), then Q <- norm(M Q), B^T = M^T Q = Q2 R2, the SVD of
+    R2^T and left = Q U^, right = Q2 V^.  -> (left [n, r], s [r], right [m, r], dropped int32 [2 n_iter + 2], info)."""
+    n, m = csr[0].numel() - 1, csr_t[0].numel() - 1
+    dropped = []
+
+    def norm(Y):
+        Q, R, d = psvd_orthonormalize(Y)
+        dropped.append(d)
+        return Q, R
+
+    Q = omega
+    for _ in range(int(n_iter)):
+        Q, _ = norm(psvd_spmm(csr, m, Q))
+        Q, _ = norm(psvd_spmm(csr_t, n, Q))
+    Q, _ = norm(psvd_spmm(csr, m, Q))
+    Q2, R2 = norm(psvd_spmm(csr_t, n, Q))
+    Uh, s, Vh, info = psvd_jacobi(R2.t().contiguous(), max_sweeps)
+    return psvd_gemm(Q, Uh), s, psvd_gemm(Q2, Vh), torch.cat(dropped), info
+
+
+def psvd_rank(user_vec, item_vec, users, items=None, topk=0):
+    """float64 scores [B, C] of users [B] at the candidates items [B, C] (None: every item) and, for topk > 0, the ids
+    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_psvd_rank).
+    -> (scores, ids or None)"""
+    up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
+    U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
+    if item_vec.shape[1] != k:
+        raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
+    users = users.to(torch.int64).contiguous()
+    B = users.numel()
+    if items is not None:
+        items = items.to(torch.int64).contiguous()
+        if items.dim() != 2 or items.shape[0] != B:
+            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
+        Cn = int(items.shape[1])
+    else:
+        Cn = I
+    dev = user_vec.device
+    scores = torch.empty(B, Cn, dtype=torch.float64, device=dev)
+    kk = min(int(topk), Cn)
+    ids = torch.empty(B, kk, dtype=torch.int64, device=dev) if kk > 0 else None
+    check(lib.daisy_psvd_rank(up, ip, U, I, k, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"), Cn, kk,
+                              _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
+    return scores, ids

@@ -912,6 +912,54 @@ int daisy_slim_scores(const int64_t *row_ptr, const int32_t *col, const float *v
                       const int64_t *w_ptr, const int32_t *w_row, const float *w_val, const int64_t *users, int64_t B,
                       const int64_t *items, int64_t C, float *out, int32_t path, daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * PureSVD (daisy/model/PureSVDRecommender.py, PureSVD): scikit-learn's randomized_svd of the rating matrix, restated
+ * as sparse x tall-skinny products, Cholesky-QR2 orthonormalisation and one small one-sided Jacobi SVD, all in fp64
+ * (csrc/puresvd.hip).  Dense matrices are fp64, row-major, on the device; c (columns of a tall-skinny
+ * matrix, sides of the small square ones) is at most DAISY_PSVD_MAX_C.  Every result is reproducible run to run: no
+ * floating-point atomics, every sum in a fixed order.
+ * ---------------------------------------------------------------------- */
+#define DAISY_PSVD_MAX_C 256
+enum { DAISY_PSVD_CONVERGED = 0, DAISY_PSVD_NOT_CONVERGED = 1 };
+/* Y[n_rows, c] = A X, A the CSR of daisy_slim_gram's layout ([n_rows, n_cols], val widened to fp64 on load), X fp64
+ * [n_cols, c]: one workgroup per row, a row's non-zeros accumulated in stored order; an empty row writes zeros. */
+int daisy_psvd_spmm(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows, int64_t n_cols,
+                    const double *X, int32_t c, double *Y, daisy_stream_t stream);
+/* rows per block of daisy_psvd_gram for block_rows <= 0 (the default: 256, or more so that there are at most 256
+ * blocks), else block_rows rounded up to a multiple of 4; and the bytes of its workspace (one [c, c] partial product
+ * per block).  0 on bad arguments. */
+int64_t daisy_psvd_gram_block_rows(int64_t n, int64_t block_rows);
+size_t daisy_psvd_gram_workspace_bytes(int64_t n, int32_t c, int64_t block_rows);
+/* G[c, c] = Y^T Y of Y [n, c] on the fp64 MFMA (v_mfma_f64_16x16x4_f64): every block of rows writes its partial
+ * product, a second pass adds the partial products in block order.  G is bitwise symmetric. */
+int daisy_psvd_gram(const double *Y, int64_t n, int32_t c, double *G, int64_t block_rows, void *workspace,
+                    size_t workspace_bytes, daisy_stream_t stream);
+/* The upper-triangular R [c, c] with R^T R = G (one workgroup), for G = Y^T Y of a Y with n rows.  Column j is DROPPED
+ * when its pivot d_j = G_jj - sum_{i<j} R_ij^2 is not > 64 n eps G_jj (eps = 2^-52): R_jj = 0 and the rest of row j is
+ * zero; the entries above the diagonal in column j are kept.  Rinv [c, c] gets the inverse of R restricted to the kept
+ * columns (zero rows and columns for the dropped ones), *dropped (a device int32) the number of dropped columns. */
+int daisy_psvd_chol(const double *G, int32_t c, int64_t n, double *R, double *Rinv, int32_t *dropped,
+                    daisy_stream_t stream);
+/* C[n, c2] = Y[n, c] T[c, c2] on the fp64 MFMA; k ascending in every element's sum. */
+int daisy_psvd_gemm(const double *Y, const double *T, double *C, int64_t n, int32_t c, int32_t c2,
+                    daisy_stream_t stream);
+/* One-sided (Hestenes) Jacobi SVD of A [c, c] = U diag(s) V^T in one workgroup: round-robin pairs of ROWS are rotated
+ * until a whole sweep rotates nothing (|a_p . a_q| <= sqrt(c) eps |a_p| |a_q| for every pair) or max_sweeps sweeps are
+ * done.  U [c, c] (orthogonal: the product of the rotations), s [c] sorted non-increasing (ties in row order),
+ * V [c, c] (column i the right vector of s[i]; a zero column where s[i] == 0).  info int32 [2] on the device:
+ * {DAISY_PSVD_CONVERGED or DAISY_PSVD_NOT_CONVERGED, sweeps done}.  workspace: daisy_psvd_jacobi_workspace_bytes(c). */
+size_t daisy_psvd_jacobi_workspace_bytes(int32_t c);
+int daisy_psvd_jacobi(const double *A, int32_t c, int32_t max_sweeps, double *U, double *s, double *V, int32_t *info,
+                      void *workspace, size_t workspace_bytes, daisy_stream_t stream);
+/* scores[B, C] (fp64) = user_vec[users[b]] . item_vec[items[b][c]] (items == NULL: every item, C = item_num), the sum
+ * over the k factors in ascending order; then, unless out_ids == NULL (scores only), out_ids [B, min(topk, C)] = the
+ * candidates' ids (positions when items == NULL) of the largest scores, compared as fp64, ties to the lower position.
+ * One workgroup per user row.  An id out of range scores 0; a row with fewer than topk comparable scores (NaN) is
+ * filled with -1. */
+int daisy_psvd_rank(const double *user_vec, const double *item_vec, int64_t user_num, int64_t item_num, int32_t k,
+                    const int64_t *users, int64_t B, const int64_t *items, int64_t C, int32_t topk, double *scores,
+                    int64_t *out_ids, daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
