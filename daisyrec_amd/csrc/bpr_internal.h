@@ -1,5 +1,6 @@
-// Internal types shared by the training translation units (bpr_train.hip: the phase kernels; bpr_staged.hip: the staged
-// step; bpr_small.hip: the persistent small-batch epoch).  The epoch plan and the batch views are in epoch_plan.h.
+// Internal types shared by the training translation units (bpr_train.hip: the phase kernels; bpr_staged*.hip: the staged
+// step, which has bpr_staged.h of its own; bpr_small.hip: the persistent small-batch epoch).  The epoch plan and the batch
+// views are in epoch_plan.h.
 #pragma once
 
 #include "epoch_plan.h"
@@ -53,7 +54,7 @@ struct daisy_bpr_ctx {
 
 
 namespace daisy {
-// bpr_staged.hip
+// bpr_staged.hip (the step; its two passes: bpr_staged_user.hip, bpr_staged_item.hip)
 bool staged_supported(const daisy_bpr_ctx *ctx, int loss_type);
 int staged_sgd_step(daisy_bpr_ctx *ctx, float *P, float *Q, int loss_type, float gamma, float lr, float reg_1,
                     float reg_2, double *stats, double *epoch_acc, double *step_loss, hipStream_t s);
@@ -179,7 +180,7 @@ __device__ __forceinline__ void adam_row(Row<C> &w, Row<C> &m, Row<C> &v, const 
     }
 }
 
-// Optimiser of a table's row owners in the staged step (bpr_staged.hip).  SGD: w -= lr * g.  Adam (template flag): the
+// Optimiser of a table's row owners in the staged step (bpr_staged_user.hip, bpr_staged_item.hip).  SGD: w -= lr * g.  Adam (template flag): the
 // lazy form of torch.optim.Adam - the rows a step references have been brought to step t-1 before the pass
 // (daisy_bpr_staged_adam_catchup), the owner applies step t with the row's gradient and stamps last[row] = t.
 struct RowOpt {

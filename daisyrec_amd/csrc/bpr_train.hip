@@ -29,7 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bpr_internal.h"
+#include "bpr_staged.h"
 
 namespace daisy {
 
@@ -1090,16 +1090,22 @@ int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int6
     a.add(&c->partials, ((size_t)kMaxGrid * 8 + kPreBlocks) * 8);
     a.add(&c->tmp_triples, (size_t)max_batch * 12);
     // edge records: two per chunk of the user pass (B samples) or of the item pass (2B entries)
-    size_t max_chunks = 0;
+    size_t max_chunks = 0, chunks2 = 0;
     (void)dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         const size_t cu = ((size_t)max_batch + UserRunCfg<C>::E - 1) / UserRunCfg<C>::E;
         const size_t ci = (2 * (size_t)max_batch + RunCfg<C>::E - 1) / RunCfg<C>::E;
-        // staged passes: the item pass runs 128-thread workgroups (kStagedItemBlock) over 2 B entries, and its sparse
-        // flavour keeps 4 (rows of <= 8 floats per lane) or 2 (wider rows) entries per lane group in flight: that is
-        // its smallest chunk (StagedItemCfg<C, 128, true>::E)
-        const size_t e_min = (size_t)(128 / C::LPR) * (C::NE <= 8 ? 4 : 2);
-        const size_t cs = (2 * (size_t)max_batch + e_min - 1) / e_min;
+        // staged passes (bpr_staged.h): the sparse flavour of the item pass has its smallest chunks, over 2 B entries, and
+        // the user pass's B samples never make more chunks than that
+        using Sparse = StagedItemCfg<C, kStagedItemBlock, true>;
+        static_assert(Sparse::E <= StagedItemCfg<C, kStagedItemBlock>::E && Sparse::E <= 2 * StagedUserCfg<C, StagedUserBlk<C>::value>::E,
+                      "the edge records are sized by the sparse item pass");
+        const size_t cs = (2 * (size_t)max_batch + Sparse::E - 1) / Sparse::E;
+        // the item pass's own edge records in the three-launch form (256-thread workgroups, batches up to kMergeMaxBatch)
+        using Merged = StagedItemCfg<C, kBlock, true>;
+        static_assert(Merged::E <= StagedItemCfg<C, kBlock>::E, "the second set is sized by the sparse flavour too");
+        const size_t merge_b = (size_t)(max_batch < kMergeMaxBatch ? max_batch : kMergeMaxBatch);
+        chunks2 = 2 * merge_b / Merged::E + 2;
         max_chunks = (cu > ci ? cu : ci);
         if (cs > max_chunks) max_chunks = cs;
         max_chunks += 2;
@@ -1112,9 +1118,7 @@ int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int6
     a.add(&c->edge_cnt, n_edge * 16);             // staged item pass: (n_pos, n_neg, coefficient sum, -) per edge record
     const size_t n_eb = max_chunks / kEdgeBlock + 2;      // block sums of long edge chains (k_staged_item_edge_blocks)
     a.add(&c->eb_vec, n_eb * (size_t)d * 4); a.add(&c->eb_item, n_eb * 4); a.add(&c->eb_cnt, n_eb * 16); a.add(&c->eb_through, n_eb * 4);
-    // the item pass's own edge records in the three-launch form (its chunks are at least 2 entries x 16 lane groups)
-    const size_t merge_b = (size_t)(max_batch < kMergeMaxBatch ? max_batch : kMergeMaxBatch);
-    const size_t chunks2 = 2 * merge_b / 32 + 2, n_edge2 = 2 * chunks2;
+    const size_t n_edge2 = 2 * chunks2;
     a.add(&c->edge2_vec, n_edge2 * (size_t)d * 4); a.add(&c->edge2_item, n_edge2 * 4); a.add(&c->edge2_cnt, n_edge2 * 16);
     a.add(&c->edge2_whole, n_edge2 * 4);
     a.add(&c->slice_rng, (kMaxItemSlices + 1) * 8);

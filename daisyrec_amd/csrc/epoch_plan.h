@@ -38,7 +38,7 @@ struct BatchView {
     const double *halt;
 };
 
-// What the STAGED step (bpr_staged.hip) sees of the current batch.  Either layout of the epoch plan
+// What the STAGED step (bpr_staged.hip and its two passes, bpr_staged_user.hip / bpr_staged_item.hip) sees of the current batch.  Either layout of the epoch plan
 // can feed it:
 //   sample s in [0,B):  partitioned layout: s_rec[s] = {user, pos item, neg item, epoch position}, stage slot of the sample
 //                       = position - pos_base;   sorted layout (s_rec == NULL): user = s_user[s] & umask, (pos item, neg

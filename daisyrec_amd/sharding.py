@@ -14,7 +14,7 @@ AbstractRecommender.py:99); this is the data-parallel form of the same step:
 The union of the per-rank batches is one global batch: the result equals the single-GPU
 step on that union up to fp32 summation order.
 
-STAGED protocol (item_mode 'fused', the default; kernels of csrc/bpr_staged.hip).  The item
+STAGED protocol (item_mode 'fused', the default; kernels of csrc/bpr_staged_*.hip).  The item
 exchange costs I/N rows of apply work per rank instead of I, and its wire volume is the
 reduce-scatter + all-gather pair a ring all-reduce is made of:
 

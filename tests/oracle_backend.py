@@ -103,7 +103,7 @@ class OracleContext:
         Q.sub_(lr * self.gQ)
         self.gQ.zero_()
 
-    # ---- the staged phases (csrc/bpr_staged.hip), restated: prenorm -> user -> finalize -> item -> apply
+    # ---- the staged phases (csrc/bpr_staged_user.hip, csrc/bpr_staged_item.hip), restated: prenorm -> user -> finalize -> item -> apply
     def staged_prenorm(self, P):
         pu = P.numpy().astype(np.float64)[self.u]
         self.stats[13] = (pu * pu).sum()

@@ -1,4 +1,4 @@
-"""Randomised differential test of the staged epoch (csrc/bpr_staged.hip) at the sizes between the unit cases and the
+"""Randomised differential test of the staged epoch (csrc/bpr_staged*.hip) at the sizes between the unit cases and the
 bench: batches of 1 ... 200 000 samples, tables of 1 ... 80 000 rows, any factor count, uniform and Zipf ids (hot users
 and items: long runs, long segments, long edge chains), every loss, SGD and torch's Adam, the item pass's flavours and
 launch forms forced on and off - one epoch (up to ~3 batches, the last one partial) through the partitioned plan

@@ -1,5 +1,5 @@
-"""The partitioned epoch plan (csrc/epoch_plan.hip) and the staged step (csrc/bpr_staged.hip): index work bit-exact against
-the oracle's restatement, the step against oracle.mf_sgd_step (MFRecommender.py:63-97 + SGD) on the
+"""The partitioned epoch plan (csrc/epoch_plan.hip) and the staged step (csrc/bpr_staged.hip, bpr_staged_user.hip,
+bpr_staged_item.hip): index work bit-exact against the oracle's restatement, the step against oracle.mf_sgd_step (MFRecommender.py:63-97 + SGD) on the
 same batches, the phase form against the single call, bitwise reproducibility, id validation."""
 import numpy as np
 import pytest
@@ -127,6 +127,10 @@ def test_staged_epoch_matches_oracle(d, loss, sparse, merge, monkeypatch):
     sparse = "1": the sparse flavour of the item pass (runs of 4 entries, the Q row of every entry gathered with its
     staged row) forced onto these DENSE batches - long segments across runs and chunks, which it meets rarely where
     the library picks it by itself."""
+    _epoch_against_oracle(d, loss, sparse, merge, monkeypatch)
+
+
+def _epoch_against_oracle(d, loss, sparse, merge, monkeypatch):
     from daisyrec_amd import ops
     if sparse:
         monkeypatch.setenv("DAISY_STAGED_SPARSE", sparse)
@@ -298,6 +302,14 @@ def test_p_stream_step_at_ten_million_users():
     assert torch.equal(P1[untouched], P[untouched])
 
 
+@pytest.mark.parametrize("loss", ["BPR", "TL", "CL"])
+def test_staged_wide_rows_merged_sparse_matches_oracle(loss, monkeypatch):
+    """d = 260: rows of four float4 over 32 lanes, whose sparse chunks in the three-launch form are the smallest of all
+    (16 entries) - the context's second set of edge records is sized for them.  The epoch of
+    test_staged_epoch_matches_oracle with both the sparse flavour and the three-launch form forced."""
+    _epoch_against_oracle(260, loss, "1", "1", monkeypatch)
+
+
 @pytest.mark.parametrize("d,loss", [(64, "BPR"), (32, "TL"), (100, "BPR"), (64, "CL"), (20, "SL"), (128, "HL")])
 def test_staged_adam_epochs_match_the_dense_oracle(d, loss):
     """torch.optim.Adam applied by the row owners of the staged step (lazy: catch-up of the referenced rows, step t on the
@@ -419,6 +431,64 @@ def test_staged_large_batch_against_chunked_and_reproducible(merge, monkeypatch)
     assert np.array_equal((a[0] != P0).any(1), (c[0] != P0).any(1))
     assert np.array_equal((a[1] != Q0).any(1), (c[1] != Q0).any(1))
     plan.close(); plan0.close(); index.close()
+
+
+def _merge_edge_epoch(P0, Q0, B, mode, pl):
+    from daisyrec_amd import ops
+    P, Q = torch.from_numpy(P0).to(DEV), torch.from_numpy(Q0).to(DEV)
+    ctx = ops.BprContext(B, 64, P0.shape[0], Q0.shape[0])
+    ctx.fit_epoch_sgd(pl, P, Q, 0.01, 1e-3, 1e-3, item_mode=ops.ITEM_MODES[mode])
+    torch.cuda.synchronize()
+    out = (P.cpu().numpy(), Q.cpu().numpy(), float(ctx.epoch_acc[0].cpu()))
+    ctx.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def merge_edge_cases():
+    """B -> (tables, the partitioned plan, the chunked phase kernels' epoch on the sorted plan): built once per batch size"""
+    from daisyrec_amd import ops
+    cases, owned = {}, []
+    for B in (32768, 32800):
+        U, I, d, n = 5000, 2000, 64, 2 * B
+        tri = _triples(n, U, I, 7, sort=True)
+        tri[:3000, 0] = 7                      # one long user run
+        tri[3000:5000, 1] = 11                 # one hot item
+        tri = tri[np.argsort(tri[:, 0], kind="stable")]
+        t_dev = torch.from_numpy(tri).to(DEV)
+        P0, Q0 = _tables(U, I, d, 9, 0.05)
+        index, plan, plan0 = ops.TrainIndex(t_dev, U, I), ops.EpochPlan(n, U, I), ops.EpochPlan(n, U, I)
+        plan.build_indexed(index, B, order="feistel", seed=1, epoch=0)
+        plan0.build(t_dev, B, order="feistel", seed=1, epoch=0, user_sorted=True)
+        cases[B] = (P0, Q0, plan, _merge_edge_epoch(P0, Q0, B, "chunked", plan0))
+        owned += [index, plan, plan0]
+    yield cases
+    for x in owned:
+        x.close()
+
+
+@pytest.mark.parametrize("merge", [None, "0", "1"])
+@pytest.mark.parametrize("B", [32768, 32800])
+def test_staged_merge_decision_at_its_threshold(B, merge, monkeypatch, merge_edge_cases):
+    """The three-launch form is chosen before the user pass is launched, from its grid: at d = 64 a user-pass chunk is 32
+    samples (StagedUserCfg: 128 threads / 16 lanes per row x runs of 4), so B = 32 768 makes exactly 1 024 user-pass
+    workgroups - the last size that merges by itself - and B = 32 800 makes 1 025, the first that does not; merge = "0" /
+    "1" force the four- / three-launch form at both.  One epoch of two batches (the first one's item pass carries the
+    second one's pre-norm): the fused step on the partitioned plan equals the chunked phase kernels on the sorted plan to
+    round-off (the tolerances of test_staged_large_batch_against_chunked_and_reproducible), moves the same rows, and two
+    runs give identical bits.  Which form ran is not observable from here: the test holds both forms to the same result
+    on both sides of the threshold, it does not assert where the threshold lies."""
+    if merge is not None:
+        monkeypatch.setenv("DAISY_STAGED_MERGE", merge)
+    else:
+        monkeypatch.delenv("DAISY_STAGED_MERGE", raising=False)
+    P0, Q0, plan, c = merge_edge_cases[B]
+    a, b = _merge_edge_epoch(P0, Q0, B, "fused", plan), _merge_edge_epoch(P0, Q0, B, "fused", plan)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]      # reproducible
+    assert abs(a[2] - c[2]) <= 1e-6 * abs(c[2])
+    assert np.abs(a[0] - c[0]).max() < 2e-6 and np.abs(a[1] - c[1]).max() < 2e-6
+    assert np.array_equal((a[0] != P0).any(1), (c[0] != P0).any(1))
+    assert np.array_equal((a[1] != Q0).any(1), (c[1] != Q0).any(1))
 
 
 def test_staged_phases_equal_single_call():
