@@ -77,6 +77,7 @@ VAE_STATS_LEN = 8
 SLIM_LDS_ITEMS, SLIM_MAX_TOPK = 9984, 1024
 SLIM_PATHS = {"auto": 0, "lds": 1, "global": 2}
 PSVD_MAX_C, PSVD_CONVERGED, PSVD_NOT_CONVERGED = 256, 0, 1
+EASE_BLOCK = 64
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
@@ -214,6 +215,14 @@ SIGNATURES = {
     "daisy_psvd_jacobi_workspace_bytes": (_sz, [_i32]),
     "daisy_psvd_jacobi": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "daisy_psvd_rank": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "daisy_ease_workspace_bytes": (_sz, [_i64]),
+    "daisy_ease_fit_bytes": (_sz, [_i64]),
+    "daisy_ease_fits": (C.c_int, [_i64, _sz]),
+    "daisy_ease_system": (C.c_int, [_p, _i64, C.c_double, _p, _p]),
+    "daisy_ease_potrf": (C.c_int, [_p, _i64, _p, _p, _sz, _p]),
+    "daisy_ease_potri": (C.c_int, [_p, _i64, _p, _p, _p, _sz, _p]),
+    "daisy_ease_weights": (C.c_int, [_p, _i64, _p, _p, _sz, _p]),
+    "daisy_ease_rank": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

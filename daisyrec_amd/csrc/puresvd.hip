@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "topk_f64.h"
 
 namespace daisy {
 namespace {
@@ -270,15 +271,13 @@ __global__ __launch_bounds__(kJacobiBlock) void k_psvd_jacobi(const double *__re
 }
 
 // ---- scores and top-k on the fp64 keys ------------------------------------------------------------------------------------
-// One workgroup per user row: the row's scores (thread per candidate, factors in ascending order), then topk rounds of
-// "the largest score after the previous pick" in the order (score descending, position ascending).
+// One workgroup per user row: the row's scores (thread per candidate, factors in ascending order), then the top-k of
+// topk_f64.h (score descending, position ascending).
 __global__ __launch_bounds__(kBlock) void k_psvd_rank(const double *__restrict__ user_vec, const double *__restrict__ item_vec,
                                                       int64_t U, int64_t I, int k, const int64_t *__restrict__ users,
                                                       const int64_t *__restrict__ items, int64_t C, int topk,
                                                       double *scores, int64_t *__restrict__ out_ids) {
-    __shared__ double s_v[kBlock / kWave];
-    __shared__ long long s_i[kBlock / kWave];
-    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+    const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int64_t u = users[b];
     const bool valid = u >= 0 && u < U;
@@ -294,42 +293,7 @@ __global__ __launch_bounds__(kBlock) void k_psvd_rank(const double *__restrict__
         row[cidx] = s;
     }
     if (!out_ids) return;
-    __syncthreads();
-    double pv = 0.0;
-    long long pp = -1;                  // the previous pick; pp < 0: none yet
-    for (int sel = 0; sel < topk; ++sel) {
-        double bv = 0.0;
-        long long bi = LLONG_MAX;
-        for (int64_t cidx = tid; cidx < C; cidx += kBlock) {           // ascending position: the first maximum is the lowest
-            const double v = row[cidx];
-            const bool elig = (pp < 0) ? (v == v) : (v < pv || (v == pv && cidx > pp));
-            if (elig && (bi == LLONG_MAX || v > bv)) { bv = v; bi = cidx; }
-        }
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off, kWave);
-            const long long oi = __shfl_xor(bi, off, kWave);
-            if (oi != LLONG_MAX && (bi == LLONG_MAX || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-        __syncthreads();
-        bv = s_v[0];
-        bi = s_i[0];
-#pragma unroll
-        for (int wv = 1; wv < kBlock / kWave; ++wv) {
-            const double ov = s_v[wv];
-            const long long oi = s_i[wv];
-            if (oi != LLONG_MAX && (bi == LLONG_MAX || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-        }
-        __syncthreads();
-        if (bi == LLONG_MAX) {                                        // nothing comparable left
-            for (int t = sel + tid; t < topk; t += kBlock) out_ids[b * topk + t] = -1;
-            return;
-        }
-        if (tid == 0) out_ids[b * topk + sel] = items ? items[b * C + bi] : (int64_t)bi;
-        pv = bv;
-        pp = bi;
-    }
+    topk_f64_select(row, C, topk, items ? items + b * C : nullptr, out_ids + b * topk);
 }
 
 inline int64_t gram_block_rows(int64_t n, int64_t block_rows) {

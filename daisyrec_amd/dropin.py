@@ -60,6 +60,12 @@ def install(sampler=False, front_end=False):
         ref_psvd.PureSVD = PureSVD
     except ImportError:
         pass
+    from .model.EASERecommender import EASE
+    try:                                   # the reference module imports scipy
+        ref_ease = importlib.import_module("daisy.model.EASERecommender")
+        ref_ease.EASE = EASE
+    except ImportError:
+        pass
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -9,3 +9,4 @@ from .Item2VecRecommender import Item2Vec  # noqa: F401
 from .VAECFRecommender import VAECF  # noqa: F401
 from .SLiMRecommender import SLiM  # noqa: F401
 from .PureSVDRecommender import PureSVD  # noqa: F401
+from .EASERecommender import EASE  # noqa: F401

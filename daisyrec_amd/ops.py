@@ -1585,3 +1585,101 @@ def psvd_rank(user_vec, item_vec, users, items=None, topk=0):
     check(lib.daisy_psvd_rank(up, ip, U, I, k, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"), Cn, kk,
                               _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
     return scores, ids
+
+
+# ---- EASE (csrc/ease.hip; EASERecommender.py) ------------------------------------------------------------------
+def _ease_square(t, name):
+    p = _f64(t, name)
+    n = int(t.shape[0])
+    if t.shape[1] != n:
+        raise ValueError(f"{name}: expected a square matrix, got {tuple(t.shape)}")
+    return p, n
+
+
+def ease_workspace(n, device):
+    """The small workspace potrf, potri and weights share (daisy_ease_workspace_bytes): the inverses of the diagonal
+    blocks, then diag(P)."""
+    return _ws(lib.daisy_ease_workspace_bytes(int(n)), device)
+
+
+def ease_system(G, reg):
+    """A = (double) G + reg I, float64 [I, I] (daisy_ease_system); G: slim_gram's float32 matrix."""
+    if not isinstance(G, torch.Tensor) or G.dim() != 2 or G.shape[0] != G.shape[1]:
+        raise ValueError("G: expected a square 2-D torch.Tensor")
+    n = int(G.shape[0])
+    A = torch.empty(n, n, dtype=torch.float64, device=G.device)
+    check(lib.daisy_ease_system(_ptr(G, torch.float32, "G"), n, float(reg), _ptr(A, torch.float64, "A"), _stream()))
+    return A
+
+
+def ease_potrf(A, ws=None):
+    """The lower Cholesky factor of A in place (daisy_ease_potrf) -> (A, info, ws): only A's lower triangle is read and
+    written; info an int32 device tensor [1]: 0, or 1 + the first column whose pivot is not positive; ws: the workspace
+    ease_potri needs."""
+    ap, n = _ease_square(A, "A")
+    ws = ease_workspace(n, A.device) if ws is None else ws
+    info = torch.zeros(1, dtype=torch.int32, device=A.device)
+    check(lib.daisy_ease_potrf(ap, n, _ptr(info, torch.int32, "info"), _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return A, info, ws
+
+
+def ease_potri(L, ws, inplace=False):
+    """P = (L L^T)^-1 from ease_potrf's factor and workspace (daisy_ease_potri), bitwise symmetric; inplace: P takes L's
+    storage.  One [n, n] scratch matrix (L^-1) lives for the duration of the call."""
+    lp, n = _ease_square(L, "L")
+    T = torch.empty_like(L)
+    P = L if inplace else torch.empty_like(L)
+    check(lib.daisy_ease_potri(lp, n, _ptr(T, torch.float64, "T"), _ptr(P, torch.float64, "P"), _ptr(ws, torch.uint8, "ws"),
+                               ws.numel(), _stream()))
+    return P
+
+
+def ease_weights(P, ws=None, inplace=False):
+    """B[i, j] = -P[i, j] / P[j, j] with a zero diagonal (daisy_ease_weights); inplace: B takes P's storage."""
+    pp, n = _ease_square(P, "P")
+    ws = ease_workspace(n, P.device) if ws is None else ws
+    B = P if inplace else torch.empty_like(P)
+    check(lib.daisy_ease_weights(pp, n, _ptr(B, torch.float64, "B"), _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return B
+
+
+def ease_fit(csr, item_num, reg, offered_bytes=None):
+    """EASERecommender.py:37-43 on the device -> (B float64 [I, I], info int32 [1]): slim_gram, ease_system, ease_potrf,
+    ease_potri, ease_weights; the fp32 Gram matrix is freed once the system exists, the factor, the inverse and B share
+    one buffer.  offered_bytes: what the fit may take (default: the device's free memory); a problem whose two fp64
+    buffers do not fit is refused before anything is allocated."""
+    I = int(item_num)
+    dev = csr[0].device
+    if offered_bytes is None:
+        with torch.cuda.device(dev):
+            offered_bytes = torch.cuda.mem_get_info()[0]
+    check(lib.daisy_ease_fits(I, int(offered_bytes)))
+    G = slim_gram(csr, I, offered_bytes=offered_bytes)
+    A = ease_system(G, reg)
+    del G
+    A, info, ws = ease_potrf(A)
+    P = ease_potri(A, ws, inplace=True)
+    return ease_weights(P, ws, inplace=True), info
+
+
+def ease_rank(csr, W, users, items=None, topk=0):
+    """float64 scores [B, C] = X[users] W at the candidates items [B, C] (None: every item) and, for topk > 0, the ids
+    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_ease_rank).
+    csr: slim_csr's triple of X; W float64 [I, I].  -> (scores, ids or None)"""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    wp, I = _ease_square(W, "W")
+    users = users.to(torch.int64).contiguous()
+    B = users.numel()
+    if items is not None:
+        items = items.to(torch.int64).contiguous()
+        if items.dim() != 2 or items.shape[0] != B:
+            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
+        Cn = int(items.shape[1])
+    else:
+        Cn = I
+    scores = torch.empty(B, Cn, dtype=torch.float64, device=W.device)
+    kk = min(int(topk), Cn)
+    ids = torch.empty(B, kk, dtype=torch.int64, device=W.device) if kk > 0 else None
+    check(lib.daisy_ease_rank(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"),
+                              Cn, kk, _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
+    return scores, ids

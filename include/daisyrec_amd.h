@@ -960,6 +960,54 @@ int daisy_psvd_rank(const double *user_vec, const double *item_vec, int64_t user
                     const int64_t *users, int64_t B, const int64_t *items, int64_t C, int32_t topk, double *scores,
                     int64_t *out_ids, daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * EASE (daisy/model/EASERecommender.py, EASE): B = -P / diag(P) with a zero diagonal, P = (X^T X + reg I)^-1, by a
+ * blocked fp64 Cholesky factorisation, the blocked inverse of the factor and one product, all on the fp64 MFMA
+ * (csrc/ease.hip).  Matrices are fp64, row-major [n, n], on the device; every element index is 64-bit.
+ * Every result is reproducible run to run: no atomics, every element's sum over k ascending in a fixed workgroup.
+ * The stages share one small workspace of daisy_ease_workspace_bytes(n) bytes: potrf writes the inverses of the diagonal
+ * blocks into it, potri reads them, weights keeps diag(P) in it.
+ * ---------------------------------------------------------------------- */
+#define DAISY_EASE_BLOCK 64
+/* bytes of the shared workspace (ceil(n / 64) blocks of 64 x 64 doubles, plus n doubles); 0 on bad arguments */
+size_t daisy_ease_workspace_bytes(int64_t item_num);
+/* bytes a fit holds at its peak (during potri): TWO fp64 [item_num, item_num] buffers - one that holds the system, then
+ * L, then P, then B in place, and one for L^-1 - plus the workspace.  (Before that, the fp32 Gram matrix of
+ * daisy_slim_gram and the system: 1.5 such buffers.)  0 on bad arguments. */
+size_t daisy_ease_fit_bytes(int64_t item_num);
+/* DAISY_OK when daisy_ease_fit_bytes(item_num) <= offered_bytes, else DAISY_ERR_ARG with the sizes in
+ * daisy_last_error(); makes no HIP call: callers refuse a fit before anything is allocated. */
+int daisy_ease_fits(int64_t item_num, size_t offered_bytes);
+/* EASERecommender.py:37-39: A = (double) G + reg I, G the fp32 [item_num, item_num] output of daisy_slim_gram. */
+int daisy_ease_system(const float *G, int64_t item_num, double reg, double *A, daisy_stream_t stream);
+/* First half of EASERecommender.py:41 (np.linalg.inv): the lower Cholesky factor A = L L^T in place, right-looking
+ * with blocks of DAISY_EASE_BLOCK: (a) one workgroup factors the diagonal block in LDS and writes its triangular inverse
+ * to the workspace, (b) the panel below it is solved against the block (products between 16-column groups on the fp64
+ * MFMA, the 16 x 16 diagonal tiles by substitution: exact when the factor is an integer matrix), (c) the trailing
+ * matrix loses L21 L21^T on the fp64 MFMA, lower tiles only.  Only A's lower triangle is read; the strict upper
+ * triangle is left as it was.  *info (a device int32): 0, or 1 + the first column whose pivot is not > 0 or not a
+ * number (what follows that column in L is then meaningless). */
+int daisy_ease_potrf(double *A, int64_t n, int32_t *info, void *workspace, size_t workspace_bytes, daisy_stream_t stream);
+/* Second half of EASERecommender.py:41: from L (daisy_ease_potrf, with the workspace it filled) T = L^-1 block row by
+ * block row (T[i, j] = -Dinv_i sum_k L[i, k] T[k, j] on the fp64 MFMA; T is scratch [n, n], its blocks above the
+ * diagonal are not written), then P = T^T T: the tiles on and above the diagonal are computed and mirrored, so P is
+ * bitwise symmetric.  P may be L's buffer; T must be one of its own. */
+int daisy_ease_potri(const double *L, int64_t n, double *T, double *P, const void *workspace, size_t workspace_bytes,
+                     daisy_stream_t stream);
+/* EASERecommender.py:42-43: B[i, j] = -P[i, j] / P[j, j], B[j, j] = 0.  B may be P's buffer. */
+int daisy_ease_weights(const double *P, int64_t n, double *B, void *workspace, size_t workspace_bytes,
+                       daisy_stream_t stream);
+/* EASERecommender.py:49-71 (predict, rank, full_rank), arguments as daisy_psvd_rank: scores[B, C] (fp64) =
+ * sum over the CSR entries (r, v) of row users[b] of X, in stored (ascending item) order, of (double) v * W[r, item], at
+ * the candidates items[B][C] (items == NULL: every item, C = item_num); then, unless out_ids == NULL (scores only),
+ * out_ids [B, min(topk, C)] = the candidates' ids (positions when items == NULL) of the largest scores, compared as
+ * fp64, ties to the lower position.  One workgroup per user row.  A user or item id out of range scores 0; a row with
+ * fewer than topk comparable scores (NaN) is filled with -1.  X: the CSR of daisy_slim_gram's layout; W fp64
+ * [item_num, item_num]. */
+int daisy_ease_rank(const int64_t *row_ptr, const int32_t *col, const float *val, const double *W, int64_t user_num,
+                    int64_t item_num, const int64_t *users, int64_t B, const int64_t *items, int64_t C, int32_t topk,
+                    double *scores, int64_t *out_ids, daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
