@@ -48,6 +48,31 @@ class NeumfParams(C.Structure):
 
 _pp = C.POINTER(NeumfParams)
 
+GEMM_LAUNCH, GEMM_LAUNCH_H, GEMM_LAUNCH_PAIR = 0, 1, 2
+GEMM_EPI_STORE, GEMM_EPI_BIAS_RELU, GEMM_EPI_GATE, GEMM_EPI_ATOMIC = 0, 1, 2, 3
+GEMM_F32, GEMM_BF16IN, GEMM_H, GEMM_PAIR = 0, 1, 2, 3          # kernel family in daisy_gemm_desc.path
+
+
+class GemmDesc(C.Structure):
+    """daisy_gemm_desc: one product of daisy_gemm_case (include/daisyrec_amd.h)."""
+    _fields_ = [("launcher", C.c_int32), ("epilogue", C.c_int32), ("bf16", C.c_int32), ("c_bf16", C.c_int32),
+                ("A", _p), ("B", _p), ("C", _p), ("bias", _p), ("gate", _p),
+                ("sam", C.c_int64), ("sak", C.c_int64), ("sbn", C.c_int64), ("sbk", C.c_int64),
+                ("ldc", C.c_int64), ("scn", C.c_int64), ("ldg", C.c_int64),
+                ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("k_chunk", C.c_int64), ("slice_stride", C.c_int64),
+                ("n_A", C.c_int64), ("n_B", C.c_int64), ("n_C", C.c_int64), ("n_bias", C.c_int64), ("n_gate", C.c_int64),
+                ("gate_scale", C.c_float), ("drop_p", C.c_float), ("drop_seed", C.c_uint64),
+                ("drop_stream", C.c_uint32), ("dry_run", C.c_int32), ("path", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_gd = C.POINTER(GemmDesc)
+
+
+def gemm_path(word):
+    """daisy_gemm_desc.path decoded: (family, WN, FAST, DROP, AK, BK, k slices, k slices of a pair's second product)."""
+    w = int(word)
+    return (w & 3, (w >> 2) & 3, (w >> 4) & 1, (w >> 5) & 1, (w >> 6) & 1, (w >> 7) & 1, (w >> 8) & 0xFFF, (w >> 20) & 0xFFF)
+
 NFM_MAX_LAYERS, NFM_MAX_FACTORS, NFM_DROP_STREAM, NFM_SMALL_MAX_B = 8, 256, 0x300, 256
 NFM_PATHS = {"auto": 0, "small": 1, "layered": 2}
 NFM_ACT = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
@@ -167,6 +192,7 @@ SIGNATURES = {
     "daisy_gemm_nt_bf16": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p]),
     "daisy_gemm_tn_bf16": (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _i64, _p]),
     "daisy_gemm_nt": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "daisy_gemm_case": (C.c_int, [_gd, _gd, _p]),
     "daisy_lgcn_graph_create": (C.c_int, [C.POINTER(_p), _p, _p, _i64, _i64, _i64, _p]),
     "daisy_lgcn_graph_destroy": (C.c_int, [_p]),
     "daisy_lgcn_graph_nnz": (_i64, [_p]),

@@ -32,6 +32,27 @@ struct GemmOp {
     uint16_t *C16;
 };
 
+// What a launcher decided for one GemmOp: the kernel instantiation and its grid.  resolve_gemm / resolve_gemm_h /
+// resolve_gemm_pair (gemm.hip) fill it - and finish the op: k_chunk clamped to K, vec_a / vec_b set - before anything
+// is launched; the launch step only reads it.  daisy_gemm_case reports word().
+enum { GEMM_F32 = 0, GEMM_BF16IN = 1, GEMM_H = 2, GEMM_PAIR = 3 };
+struct GemmPath {
+    int family;                           // GEMM_*: k_gemm, k_gemm_bf16, k_gemm_h, k_gemm_pair
+    int wn;                               // 32-column MFMA blocks per wave: 1 (64-column tiles) or 2 (128)
+    bool fast, drop;                      // template arguments FAST (always set for k_gemm_bf16; k_gemm_h and the pair have none), DROP
+    bool ak, bk;                          // k_gemm_h: operand A / B is contiguous along k
+    unsigned gx, gy, splits;              // the grid; splits = k slices (pair: of the first product)
+    unsigned ax, splits_b;                // pair: row tiles of the first product, k slices of the second
+    // family | wn << 2 | fast << 4 | drop << 5 | ak << 6 | bk << 7 | splits << 8 | splits_b << 20  (12 bits per slice count)
+    uint32_t word() const {
+        return (uint32_t)family | (uint32_t)wn << 2 | (uint32_t)fast << 4 | (uint32_t)drop << 5 | (uint32_t)ak << 6 |
+               (uint32_t)bk << 7 | (splits & 0xFFFu) << 8 | (splits_b & 0xFFFu) << 20;
+    }
+};
+GemmPath resolve_gemm(GemmOp &op, int epi);
+GemmPath resolve_gemm_h(GemmOp &op, int epi);
+GemmPath resolve_gemm_pair(GemmOp &a, GemmOp &b);
+
 // The launchers exist for the epilogues their callers use (instantiated in gemm.hip; another one is a link error):
 //   launch_gemm       STORE, BIAS_RELU, GATE, ATOMIC: fp32 storage (op.bf16: bf16 MFMA inputs where the shape allows it)
 //   launch_gemm_h     BIAS_RELU, GATE, ATOMIC: bf16 storage, only for shapes gemm_h_ok accepts

@@ -570,31 +570,54 @@ bool gemm_h_ok(const GemmOp &op) {
            al(op.A16, op.sam, op.sak) && al(op.B16, op.sbn, op.sbk);
 }
 
-template <int EPI>
-void launch_gemm_h(GemmOp op, hipStream_t s) {
+// k slices of an op, and its k_chunk clamped to K (the first thing every resolve step does)
+static unsigned take_splits(GemmOp &op) {
     const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
     if (op.k_chunk >= op.K) op.k_chunk = op.K;
-    const int bn = (op.N > 64) ? 128 : 64;
-    dim3 grid((unsigned)(op.M / kGemmBM), (unsigned)(op.N / bn), (unsigned)splits);
+    return (unsigned)splits;
+}
+static bool epi_can_drop(int epi) { return epi == EPI_BIAS_RELU || epi == EPI_GATE; }
+
+GemmPath resolve_gemm_h(GemmOp &op, int epi) {
+    GemmPath p{};
+    p.family = GEMM_H;
+    p.splits = take_splits(op);
+    p.wn = (op.N > 64) ? 2 : 1;
+    p.gx = (unsigned)(op.M / kGemmBM); p.gy = (unsigned)(op.N / (64 * p.wn));
+    p.drop = epi_can_drop(epi) && op.drop_thresh != 0;
+    // the three operand layouts the tower uses: forward X (k) x W (k), input gradient dZ (k) x W^T (rows), weight
+    // gradient dZ^T (rows) x X^T (rows); (rows, k) is refused by gemm_h_ok
+    p.ak = op.sak == 1;
+    p.bk = p.ak && op.sbk == 1;
+    return p;
+}
+
+template <int EPI>
+static void run_gemm_h(const GemmOp &op, const GemmPath &p, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.splits);
     constexpr bool can_drop = (EPI == EPI_BIAS_RELU || EPI == EPI_GATE);
-    const bool drop = can_drop && op.drop_thresh != 0;
-    const bool ak = op.sak == 1, bk = op.sbk == 1;
     auto go = [&](auto wn_c, auto drop_c, auto ak_c, auto bk_c) {
         hipLaunchKernelGGL((k_gemm_h<decltype(wn_c)::value, EPI, decltype(drop_c)::value, decltype(ak_c)::value,
                                      decltype(bk_c)::value>), grid, dim3(kBlock), 0, s, op);
     };
     using T = std::true_type; using F = std::false_type;
     using W1 = std::integral_constant<int, 1>; using W2 = std::integral_constant<int, 2>;
-    auto go2 = [&](auto wn_c, auto drop_c) {          // the three operand layouts the tower uses
-        if (ak && bk) go(wn_c, drop_c, T{}, T{});         // forward:          X (k) x W (k)
-        else if (ak) go(wn_c, drop_c, T{}, F{});          // input gradient:   dZ (k) x W^T (rows)
-        else go(wn_c, drop_c, F{}, F{});                  // weight gradient:  dZ^T (rows) x X^T (rows)
+    auto go2 = [&](auto wn_c, auto drop_c) {
+        if (p.ak && p.bk) go(wn_c, drop_c, T{}, T{});
+        else if (p.ak) go(wn_c, drop_c, T{}, F{});
+        else go(wn_c, drop_c, F{}, F{});
     };
-    if (op.N > 64) {
-        if constexpr (can_drop) { if (drop) go2(W2{}, T{}); else go2(W2{}, F{}); } else go2(W2{}, F{});
+    if (p.wn == 2) {
+        if constexpr (can_drop) { if (p.drop) go2(W2{}, T{}); else go2(W2{}, F{}); } else go2(W2{}, F{});
     } else {
-        if constexpr (can_drop) { if (drop) go2(W1{}, T{}); else go2(W1{}, F{}); } else go2(W1{}, F{});
+        if constexpr (can_drop) { if (p.drop) go2(W1{}, T{}); else go2(W1{}, F{}); } else go2(W1{}, F{});
     }
+}
+
+template <int EPI>
+void launch_gemm_h(GemmOp op, hipStream_t s) {
+    const GemmPath p = resolve_gemm_h(op, EPI);
+    run_gemm_h<EPI>(op, p, s);
 }
 
 // fp32 -> bf16 (round to nearest even): the per-step copy of the MLP weights, [rows][cols] as stored and (yt)
@@ -620,19 +643,33 @@ static bool vec_ok(const float *p, int64_t s_row, int64_t s_k, int64_t k_chunk) 
     return false;
 }
 
+// the part of the decision k_gemm and k_gemm_pair share: slices, float4 eligibility, tile width, row and column tiles
+static GemmPath resolve_f32_tiles(GemmOp &op) {
+    GemmPath p{};
+    p.splits = take_splits(op);
+    op.vec_a = vec_ok(op.A, op.sam, op.sak, p.splits > 1 ? op.k_chunk : 4);
+    op.vec_b = vec_ok(op.B, op.sbn, op.sbk, p.splits > 1 ? op.k_chunk : 4);
+    p.wn = (op.N > 64) ? 2 : 1;
+    const int bn = 64 * p.wn;
+    p.gx = (unsigned)((op.M + kGemmBM - 1) / kGemmBM); p.gy = (unsigned)((op.N + bn - 1) / bn);
+    return p;
+}
+
+GemmPath resolve_gemm(GemmOp &op, int epi) {
+    GemmPath p = resolve_f32_tiles(op);
+    p.fast = op.vec_a && op.vec_b && op.M % kGemmBM == 0 && op.N % (64 * p.wn) == 0 && op.K % kBK == 0 &&
+             (p.splits == 1 || op.k_chunk % kBK == 0);
+    const bool bf16 = op.bf16 && p.fast && op.K % kBK16 == 0 && (p.splits == 1 || op.k_chunk % kBK16 == 0);
+    p.family = bf16 ? GEMM_BF16IN : GEMM_F32;
+    p.drop = epi_can_drop(epi) && op.drop_thresh != 0;
+    return p;
+}
+
 template <int EPI>
-void launch_gemm(GemmOp op, hipStream_t s) {
-    const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-    if (op.k_chunk >= op.K) op.k_chunk = op.K;
-    op.vec_a = vec_ok(op.A, op.sam, op.sak, splits > 1 ? op.k_chunk : 4);
-    op.vec_b = vec_ok(op.B, op.sbn, op.sbk, splits > 1 ? op.k_chunk : 4);
-    const int bn = (op.N > 64) ? 128 : 64;
-    const bool fast = op.vec_a && op.vec_b && op.M % kGemmBM == 0 && op.N % bn == 0 && op.K % kBK == 0 &&
-                      (splits == 1 || op.k_chunk % kBK == 0);
-    dim3 grid((unsigned)((op.M + kGemmBM - 1) / kGemmBM), (unsigned)((op.N + bn - 1) / bn), (unsigned)splits);
-    const bool bf16 = op.bf16 && fast && op.K % kBK16 == 0 && (splits == 1 || op.k_chunk % kBK16 == 0);
+static void run_gemm(const GemmOp &op, const GemmPath &p, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.splits);
     auto go = [&](auto wn_c, auto fast_c, auto drop_c) {
-        if (bf16)
+        if (p.family == GEMM_BF16IN)
             hipLaunchKernelGGL((k_gemm_bf16<decltype(wn_c)::value, EPI, decltype(drop_c)::value>), grid, dim3(kBlock), 0,
                                s, op);
         else
@@ -642,14 +679,19 @@ void launch_gemm(GemmOp op, hipStream_t s) {
     using T = std::true_type; using F = std::false_type;
     using W1 = std::integral_constant<int, 1>; using W2 = std::integral_constant<int, 2>;
     constexpr bool can_drop = (EPI == EPI_BIAS_RELU || EPI == EPI_GATE);
-    const bool drop = can_drop && op.drop_thresh != 0;
-    if (op.N > 64) {
-        if (fast) { if constexpr (can_drop) { if (drop) go(W2{}, T{}, T{}); else go(W2{}, T{}, F{}); } else go(W2{}, T{}, F{}); }
-        else      { if constexpr (can_drop) { if (drop) go(W2{}, F{}, T{}); else go(W2{}, F{}, F{}); } else go(W2{}, F{}, F{}); }
+    if (p.wn == 2) {
+        if (p.fast) { if constexpr (can_drop) { if (p.drop) go(W2{}, T{}, T{}); else go(W2{}, T{}, F{}); } else go(W2{}, T{}, F{}); }
+        else        { if constexpr (can_drop) { if (p.drop) go(W2{}, F{}, T{}); else go(W2{}, F{}, F{}); } else go(W2{}, F{}, F{}); }
     } else {
-        if (fast) { if constexpr (can_drop) { if (drop) go(W1{}, T{}, T{}); else go(W1{}, T{}, F{}); } else go(W1{}, T{}, F{}); }
-        else      { if constexpr (can_drop) { if (drop) go(W1{}, F{}, T{}); else go(W1{}, F{}, F{}); } else go(W1{}, F{}, F{}); }
+        if (p.fast) { if constexpr (can_drop) { if (p.drop) go(W1{}, T{}, T{}); else go(W1{}, T{}, F{}); } else go(W1{}, T{}, F{}); }
+        else        { if constexpr (can_drop) { if (p.drop) go(W1{}, F{}, T{}); else go(W1{}, F{}, F{}); } else go(W1{}, F{}, F{}); }
     }
+}
+
+template <int EPI>
+void launch_gemm(GemmOp op, hipStream_t s) {
+    const GemmPath p = resolve_gemm(op, EPI);
+    run_gemm<EPI>(op, p, s);
 }
 
 // the fp32 product of gemm.h (csrc/vae.hip's layers): k_gemm with plain stores, or its split-k slices stored apart
@@ -669,21 +711,96 @@ void gemm_f32(const float *A, int64_t sam, int64_t sak, const float *B, int64_t 
 
 
 // two products of the same (N, tile width) in one launch (k_gemm_pair): guarded-loader kernels, fp32
+GemmPath resolve_gemm_pair(GemmOp &a, GemmOp &b) {
+    GemmPath p = resolve_f32_tiles(a);            // (tile width and column tiles from a: the two share N)
+    const GemmPath pb = resolve_f32_tiles(b);
+    p.family = GEMM_PAIR;
+    p.ax = p.gx;
+    p.gx += pb.gx;
+    p.splits_b = pb.splits;
+    return p;
+}
+
+template <int EPI>
+static void run_gemm_pair(const GemmOp &a, const GemmOp &b, const GemmPath &p, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.splits > p.splits_b ? p.splits : p.splits_b);
+    if (p.wn == 2) hipLaunchKernelGGL((k_gemm_pair<2, EPI>), grid, dim3(kBlock), 0, s, a, b, p.ax, p.splits, p.splits_b);
+    else hipLaunchKernelGGL((k_gemm_pair<1, EPI>), grid, dim3(kBlock), 0, s, a, b, p.ax, p.splits, p.splits_b);
+}
+
 template <int EPI>
 void launch_gemm_pair(GemmOp a, GemmOp b, hipStream_t s) {
-    auto prep = [](GemmOp &op) -> unsigned {
-        const int64_t splits = (op.k_chunk < op.K) ? (op.K + op.k_chunk - 1) / op.k_chunk : 1;
-        if (op.k_chunk >= op.K) op.k_chunk = op.K;
-        op.vec_a = vec_ok(op.A, op.sam, op.sak, splits > 1 ? op.k_chunk : 4);
-        op.vec_b = vec_ok(op.B, op.sbn, op.sbk, splits > 1 ? op.k_chunk : 4);
-        return (unsigned)splits;
-    };
-    const unsigned az = prep(a), bz = prep(b);
-    const int bn = (a.N > 64) ? 128 : 64;
-    const unsigned ax = (unsigned)((a.M + kGemmBM - 1) / kGemmBM), bx = (unsigned)((b.M + kGemmBM - 1) / kGemmBM);
-    const dim3 grid(ax + bx, (unsigned)((a.N + bn - 1) / bn), az > bz ? az : bz);
-    if (a.N > 64) hipLaunchKernelGGL((k_gemm_pair<2, EPI>), grid, dim3(kBlock), 0, s, a, b, ax, az, bz);
-    else hipLaunchKernelGGL((k_gemm_pair<1, EPI>), grid, dim3(kBlock), 0, s, a, b, ax, az, bz);
+    const GemmPath p = resolve_gemm_pair(a, b);
+    run_gemm_pair<EPI>(a, b, p, s);
+}
+
+// daisy_gemm_case: one descriptor -> a GemmOp.  Everything a kernel would index is checked against the element counts
+// the caller gave, and the shape against what the launcher takes, so that a wrong descriptor is an error return.
+static int gemm_case_op(const daisy_gemm_desc &d, const char *w, GemmOp &op) {
+    constexpr int64_t kMaxDim = (int64_t)1 << 24, kMaxStride = (int64_t)1 << 22;   // (products stay far inside int64; a
+                                                                                    // tile's 32-bit offsets 127*ldc + 127*scn too)
+    const int epi = d.epilogue;
+    const bool h = d.launcher == DAISY_GEMM_LAUNCH_H, pair = d.launcher == DAISY_GEMM_LAUNCH_PAIR;
+    DAISY_CHECK_ARG(d.launcher == DAISY_GEMM_LAUNCH || h || pair, "gemm_case: %s.launcher=%d", w, d.launcher);
+    const bool inst = h ? (epi == EPI_BIAS_RELU || epi == EPI_GATE || epi == EPI_ATOMIC)
+                        : pair ? (epi == EPI_STORE || epi == EPI_ATOMIC) : (epi >= EPI_STORE && epi <= EPI_ATOMIC);
+    DAISY_CHECK_ARG(inst, "gemm_case: %s: launcher %d is not instantiated for epilogue %d", w, d.launcher, epi);
+    DAISY_CHECK_ARG(d.M > 0 && d.M <= kMaxDim && d.N > 0 && d.N <= ((int64_t)1 << 20) && d.K > 0 && d.K <= kMaxDim,
+                    "gemm_case: %s: M, N, K must be positive (and at most 2^24, 2^20, 2^24)", w);
+    DAISY_CHECK_ARG(d.k_chunk > 0, "gemm_case: %s.k_chunk must be positive", w);
+    DAISY_CHECK_ARG(d.A && d.B && d.C, "gemm_case: %s: A, B or C is NULL", w);
+    auto stride_ok = [&](int64_t v) { return v > 0 && v <= kMaxStride; };
+    DAISY_CHECK_ARG(stride_ok(d.sam) && stride_ok(d.sak), "gemm_case: %s.sam / sak out of range", w);
+    DAISY_CHECK_ARG(stride_ok(d.sbn) && stride_ok(d.sbk), "gemm_case: %s.sbn / sbk out of range", w);
+    DAISY_CHECK_ARG(stride_ok(d.ldc) && d.scn >= 0 && d.scn <= kMaxStride, "gemm_case: %s.ldc / scn out of range", w);
+    const int64_t splits = (d.k_chunk < d.K) ? (d.K + d.k_chunk - 1) / d.k_chunk : 1;
+    DAISY_CHECK_ARG(splits <= 0xFFF, "gemm_case: %s.k_chunk gives %lld slices (at most 4095)", w, (long long)splits);
+    DAISY_CHECK_ARG(splits == 1 || epi == EPI_ATOMIC, "gemm_case: %s.k_chunk < K needs the ATOMIC epilogue", w);
+    DAISY_CHECK_ARG(d.slice_stride >= 0 && d.slice_stride <= ((int64_t)1 << 40) && (d.slice_stride == 0 || epi == EPI_ATOMIC),
+                    "gemm_case: %s.slice_stride is for the ATOMIC epilogue (and not negative)", w);
+    DAISY_CHECK_ARG(d.drop_p >= 0.f && d.drop_p < 1.f && (d.drop_p == 0.f || epi_can_drop(epi)),
+                    "gemm_case: %s.drop_p must be in [0, 1) and 0 unless the epilogue is BIAS_RELU or GATE", w);
+    DAISY_CHECK_ARG(!d.bf16 || d.launcher == DAISY_GEMM_LAUNCH, "gemm_case: %s.bf16 is a flag of launch_gemm", w);
+    const bool c16 = d.c_bf16 != 0;
+    DAISY_CHECK_ARG(!c16 || (h && epi != EPI_ATOMIC), "gemm_case: %s.c_bf16 needs launch_gemm_h with BIAS_RELU or GATE", w);
+    DAISY_CHECK_ARG(!c16 || d.scn <= 1, "gemm_case: %s.scn: the bf16 output has no transposed store", w);
+    const int64_t scn = d.scn ? d.scn : 1;
+    DAISY_CHECK_ARG((d.M - 1) * d.sam + (d.K - 1) * d.sak < d.n_A, "gemm_case: %s.n_A=%lld is short of the operand", w, (long long)d.n_A);
+    DAISY_CHECK_ARG((d.N - 1) * d.sbn + (d.K - 1) * d.sbk < d.n_B, "gemm_case: %s.n_B=%lld is short of the operand", w, (long long)d.n_B);
+    DAISY_CHECK_ARG((d.M - 1) * d.ldc + (d.N - 1) * scn + (splits - 1) * d.slice_stride < d.n_C,
+                    "gemm_case: %s.n_C=%lld is short of the output (%lld slices)", w, (long long)d.n_C, (long long)splits);
+    if (epi == EPI_BIAS_RELU) {
+        DAISY_CHECK_ARG(d.bias, "gemm_case: %s.bias is NULL", w);
+        DAISY_CHECK_ARG(d.N - 1 < d.n_bias, "gemm_case: %s.n_bias=%lld is short of N", w, (long long)d.n_bias);
+    }
+    const bool gated = epi == EPI_GATE && d.gate;
+    if (gated) {
+        DAISY_CHECK_ARG(stride_ok(d.ldg), "gemm_case: %s.ldg out of range", w);
+        DAISY_CHECK_ARG((d.M - 1) * d.ldg + d.N - 1 < d.n_gate, "gemm_case: %s.n_gate=%lld is short of the gate", w, (long long)d.n_gate);
+    }
+    op = GemmOp{};
+    op.sam = d.sam; op.sak = d.sak; op.sbn = d.sbn; op.sbk = d.sbk;
+    op.ldc = d.ldc; op.scn = d.scn; op.ldg = d.ldg;
+    op.M = d.M; op.N = (int)d.N; op.K = d.K; op.k_chunk = d.k_chunk; op.slice_stride = d.slice_stride;
+    op.bias = d.bias; op.gate_scale = d.gate_scale; op.bf16 = d.bf16 ? 1 : 0;
+    op.drop_thresh = keep_threshold(d.drop_p);
+    op.drop_scale = op.drop_thresh ? 1.f / (1.f - d.drop_p) : 1.f;
+    op.drop_seed = d.drop_seed; op.drop_stream = d.drop_stream;
+    if (h) {
+        op.A16 = static_cast<const uint16_t *>(d.A); op.B16 = static_cast<const uint16_t *>(d.B);
+        if (c16) { op.C16 = static_cast<uint16_t *>(d.C); op.G16 = gated ? static_cast<const uint16_t *>(d.gate) : nullptr; }
+        else { op.C = static_cast<float *>(d.C); op.gate = gated ? static_cast<const float *>(d.gate) : nullptr; }
+        DAISY_CHECK_ARG(gemm_h_ok(op), "gemm_case: %s: launch_gemm_h needs M %% 128 == 0, N %% 64 == 0 (128 when N > 64), K and k_chunk "
+                        "%% %d == 0, 16-byte aligned operands along k or along their rows, and not (A rows, B k)", w, kBKH);
+        // (the bf16 epilogue leaves and reads its gate in 16-byte pieces along the rows)
+        DAISY_CHECK_ARG(!c16 || (((uintptr_t)d.C & 15) == 0 && d.ldc % 8 == 0), "gemm_case: %s.C / ldc: the bf16 output needs 16-byte aligned rows", w);
+        DAISY_CHECK_ARG(!(c16 && gated) || (((uintptr_t)d.gate & 15) == 0 && d.ldg % 8 == 0),
+                        "gemm_case: %s.gate / ldg: the bf16 gate needs 16-byte aligned rows", w);
+    } else {
+        op.A = static_cast<const float *>(d.A); op.B = static_cast<const float *>(d.B);
+        op.C = static_cast<float *>(d.C); op.gate = gated ? static_cast<const float *>(d.gate) : nullptr;
+    }
+    return DAISY_OK;
 }
 
 template void launch_gemm<EPI_STORE>(GemmOp, hipStream_t);
@@ -744,6 +861,44 @@ int daisy_gemm_nt(const float *A, const float *B, float *C, int64_t M, int32_t N
     op.B = B; op.sbn = K; op.sbk = 1;
     op.C = C; op.ldc = N; op.M = M; op.N = N; op.K = K; op.k_chunk = K;
     launch_gemm<EPI_STORE>(op, as_stream(stream));
+    DAISY_LAUNCH_CHECK();
+    return DAISY_OK;
+}
+
+int daisy_gemm_case(daisy_gemm_desc *a, daisy_gemm_desc *b, daisy_stream_t stream) {
+    DAISY_CHECK_ARG(a, "gemm_case: NULL descriptor");
+    DAISY_CHECK_ARG((a->launcher == DAISY_GEMM_LAUNCH_PAIR) == (b != nullptr), "gemm_case: launch_gemm_pair takes two descriptors, the others one");
+    GemmOp oa, ob;
+    int rc = gemm_case_op(*a, "a", oa);
+    if (rc) return rc;
+    hipStream_t s = as_stream(stream);
+    const int epi = a->epilogue;
+    if (b) {
+        rc = gemm_case_op(*b, "b", ob);
+        if (rc) return rc;
+        DAISY_CHECK_ARG(b->launcher == DAISY_GEMM_LAUNCH_PAIR && b->epilogue == epi, "gemm_case: b.launcher / b.epilogue differ from a's");
+        DAISY_CHECK_ARG(a->N == b->N, "gemm_case: the pair needs a.N == b.N (%lld, %lld)", (long long)a->N, (long long)b->N);
+        const GemmPath p = resolve_gemm_pair(oa, ob);
+        a->path = b->path = p.word();
+        if (a->dry_run) return DAISY_OK;
+        if (epi == EPI_STORE) run_gemm_pair<EPI_STORE>(oa, ob, p, s);
+        else run_gemm_pair<EPI_ATOMIC>(oa, ob, p, s);
+    } else if (a->launcher == DAISY_GEMM_LAUNCH_H) {
+        const GemmPath p = resolve_gemm_h(oa, epi);
+        a->path = p.word();
+        if (a->dry_run) return DAISY_OK;
+        if (epi == EPI_BIAS_RELU) run_gemm_h<EPI_BIAS_RELU>(oa, p, s);
+        else if (epi == EPI_GATE) run_gemm_h<EPI_GATE>(oa, p, s);
+        else run_gemm_h<EPI_ATOMIC>(oa, p, s);
+    } else {
+        const GemmPath p = resolve_gemm(oa, epi);
+        a->path = p.word();
+        if (a->dry_run) return DAISY_OK;
+        if (epi == EPI_STORE) run_gemm<EPI_STORE>(oa, p, s);
+        else if (epi == EPI_BIAS_RELU) run_gemm<EPI_BIAS_RELU>(oa, p, s);
+        else if (epi == EPI_GATE) run_gemm<EPI_GATE>(oa, p, s);
+        else run_gemm<EPI_ATOMIC>(oa, p, s);
+    }
     DAISY_LAUNCH_CHECK();
     return DAISY_OK;
 }

@@ -956,6 +956,15 @@ def gemm_nt(A, B, bf16=False):
     return out
 
 
+def gemm_case(a, b=None):
+    """One product (or, with `b`, a pair in one launch) through the launcher its `N.GemmDesc` names (test hook): the
+    library checks every extent against the descriptor's element counts before it launches and raises ValueError
+    otherwise.  Returns the path word the launcher resolved (`N.gemm_path` decodes it).  `a.dry_run`: no GPU is touched."""
+    stream = None if a.dry_run else _stream()
+    check(lib.daisy_gemm_case(C.byref(a), C.byref(b) if b is not None else None, stream))
+    return int(a.path)
+
+
 # ------------------------------------------------------------------------------------------------
 # LightGCN (LightGCNRecommender.py) - see include/daisyrec_amd.h
 # ------------------------------------------------------------------------------------------------

@@ -607,6 +607,45 @@ int daisy_gemm_tn_bf16(const uint16_t *At, const uint16_t *Bt, float *C, int64_t
 /* same with the precision switch of daisy_neumf_ctx_set_precision */
 int daisy_gemm_nt(const float *A, const float *B, float *C, int64_t M, int32_t N, int32_t K, int32_t bf16,
                   daisy_stream_t stream);
+/* One product through any launcher of csrc/gemm.hip (test hook): C(m,n) = epilogue(sum_k A(m,k) B(n,k)) with
+ * A(m,k) = A[m*sam + k*sak], B(n,k) = B[n*sbn + k*sbk], C(m,n) = C[m*ldc + n*scn] (scn 0 means 1), strides in elements.
+ * k_chunk < K cuts the k range into slices (DAISY_GEMM_EPI_ATOMIC only): slice z is STORED at C + z*slice_stride, or,
+ * with slice_stride 0, all slices are added into C with fp32 atomics (so is a single slice).
+ * Before anything is launched every index the product can touch is checked against the element counts n_*, and the
+ * shape against what the launcher takes: a descriptor that fails is DAISY_ERR_ARG with the field's name in the message.
+ * `path` receives what the launcher resolved: family (0 k_gemm, 1 k_gemm_bf16, 2 k_gemm_h, 3 k_gemm_pair) | WN << 2 |
+ * FAST << 4 | DROP << 5 | AK << 6 | BK << 7 | k slices << 8 | (pair: k slices of the second product) << 20.
+ * dry_run != 0: check, resolve, write `path` and return - no HIP call is made and no pointer but the descriptors' own is
+ * read (the alignment of A, B, C and gate still decides the path). */
+#define DAISY_GEMM_LAUNCH 0       /* launch_gemm: fp32 storage (bf16 != 0: bf16 MFMA inputs where the shape allows) */
+#define DAISY_GEMM_LAUNCH_H 1     /* launch_gemm_h: A and B stored as bf16; C and gate bf16 (c_bf16) or fp32 */
+#define DAISY_GEMM_LAUNCH_PAIR 2  /* launch_gemm_pair: two fp32 products of the same N in one launch */
+#define DAISY_GEMM_EPI_STORE 0
+#define DAISY_GEMM_EPI_BIAS_RELU 1 /* max(acc + bias[n], 0) */
+#define DAISY_GEMM_EPI_GATE 2      /* acc * (gate[m*ldg + n] > 0 ? gate_scale : 0); gate NULL: acc */
+#define DAISY_GEMM_EPI_ATOMIC 3
+typedef struct daisy_gemm_desc {
+    int32_t launcher, epilogue;
+    int32_t bf16;                 /* DAISY_GEMM_LAUNCH: the throughput-mode flag of GemmOp */
+    int32_t c_bf16;               /* DAISY_GEMM_LAUNCH_H, BIAS_RELU / GATE: C (and gate) are bf16; 0: fp32 */
+    const void *A, *B;
+    void *C;
+    const float *bias;            /* f32[N] */
+    const void *gate;
+    int64_t sam, sak, sbn, sbk, ldc, scn, ldg;
+    int64_t M, N, K, k_chunk, slice_stride;
+    int64_t n_A, n_B, n_C, n_bias, n_gate;      /* elements of each buffer */
+    float gate_scale;
+    float drop_p;                 /* BIAS_RELU / GATE: dropout of output element m*N + n at probability drop_p (0: off) */
+    uint64_t drop_seed;
+    uint32_t drop_stream;
+    int32_t dry_run;
+    uint32_t path;                /* out */
+    uint32_t reserved;
+} daisy_gemm_desc;
+/* b != NULL: the pair a, b through launch_gemm_pair (both descriptors name DAISY_GEMM_LAUNCH_PAIR, the same epilogue -
+ * STORE or ATOMIC - and the same N); a's dry_run decides, both receive `path`. */
+int daisy_gemm_case(daisy_gemm_desc *a, daisy_gemm_desc *b, daisy_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * LightGCN (daisy/model/LightGCNRecommender.py:17-210)
