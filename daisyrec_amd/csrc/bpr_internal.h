@@ -1,6 +1,7 @@
-// Internal types shared by the training translation units (bpr_train.hip: the phase kernels; bpr_staged*.hip: the staged
-// step, which has bpr_staged.h of its own; bpr_small.hip: the persistent small-batch epoch).  The epoch plan and the batch
-// views are in epoch_plan.h.
+// Internal types shared by the training translation units (bpr_train.hip: the phase kernels, the context and the step;
+// segsum.hip: the segmented sum behind the item gradient, which has segsum.h of its own; adam_lazy.hip: lazy Adam on the
+// tables; bpr_staged*.hip: the staged step, which has bpr_staged.h of its own; bpr_small.hip: the persistent small-batch
+// epoch).  The epoch plan and the batch views are in epoch_plan.h.
 #pragma once
 
 #include "epoch_plan.h"

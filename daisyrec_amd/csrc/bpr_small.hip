@@ -77,7 +77,7 @@ __device__ __forceinline__ void lds_load_row(Row<C> &r, const float *src, int la
     }
 }
 
-// torch.optim.Adam in the persistent epoch (round 6): the exact lazy form of bpr_train.hip (adam_claim_row) / the staged
+// torch.optim.Adam in the persistent epoch (round 6): the exact lazy form of adam_lazy.hip (adam_claim_row) / the staged
 // step - last[row] = the step a row is current for, table[s] = step s's (lr / (1 - beta1^s), sqrt(1 - beta2^s)) - with the
 // phases of a step separated by workgroup barriers instead of six or seven kernel boundaries (48 us per step at B = 256):
 //   0  every distinct row of the step (heads of the user runs / of the item runs) is brought to step t-1: the zero-gradient

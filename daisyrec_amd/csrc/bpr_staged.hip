@@ -190,7 +190,7 @@ int staged_sgd_step(daisy_bpr_ctx *ctx, float *P, float *Q, int loss_type, float
 
 // ---- lazy Adam on the staged step ------------------------------------------------------------------------
 // Rows a batch references are brought to step t-1 before its forward pass (the zero-gradient replay of
-// adam_claim_row, bpr_train.hip).  Samples are grouped by user and entries sorted by item, so the first record of a
+// adam_claim_row, adam_lazy.hip).  Samples are grouped by user and entries sorted by item, so the first record of a
 // run of equal ids is the row's single owner: no atomics.  The user side also refreshes the row-norm cache.
 template <class C>
 __global__ __launch_bounds__(kBlock) void k_staged_adam_catchup(StreamView v, int d, float *__restrict__ P,

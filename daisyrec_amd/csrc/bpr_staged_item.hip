@@ -74,7 +74,7 @@ __device__ __forceinline__ void item_commit(float *__restrict__ Qo, float *__res
 }
 
 // Item pass over the staged rows (see the header comment): the run/slot/edge segmented reduction of
-// k_item_grad_chunked<DET> (bpr_train.hip) with the coefficient inside the gathered row and the commit in
+// k_item_grad_chunked (segsum.hip) with the coefficient inside the gathered row and the commit in
 // the owner.  A workgroup takes a chunk of G*RUN consecutive entries, every lane group a run of RUN.
 // MODE (see k_staged_user): premul - entry weight +/-1; plain - the sample's (dL/dpos, dL/dneg) gathered from coef;
 // point - weight 1 (a negative slot, which only the sorted layout's point-wise batches have, is inert: weight 0, not

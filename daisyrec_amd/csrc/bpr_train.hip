@@ -13,7 +13,8 @@
 // guarantees it without a copy of the tables:
 //   k_fwd          reads P,Q            writes coef, partial sums
 //   k_item_grad_*  reads P,Q            writes gQ  (side buffer; also what the
-//                                       multi-GPU path all-reduces)
+//                                       multi-GPU path all-reduces; throughput
+//                                       mode: segsum.hip, data term only)
 //   k_user         reads P[u] (owner),Q writes P[u]   (one owner per user row:
 //                                       every batch is grouped by user)
 //   k_item_apply   reads gQ,Q           writes Q, zeroes gQ
@@ -22,14 +23,15 @@
 // stores run at 5-8 TB/s, fp32 global atomics at 0.3 TB/s.  So every scatter is
 // organised around OWNERSHIP instead of atomics: the epoch plan (epoch_plan.hip)
 // hands over every batch grouped by user, plus a list of its item entries sorted
-// by item; the item gradient is then a segmented reduction over that list.
+// by item; the item gradient is then a segmented reduction over that list
+// (segsum.hip).  Lazy Adam for the tables: adam_lazy.hip.
 //
 // HBM/L2 view: a d=64 row is 256 B = 16 lanes x float4, one coalesced request
 // per quarter wave; four rows are in flight per wave instruction.
-#include <stdlib.h>
 #include <string.h>
 
 #include "bpr_staged.h"
+#include "segsum.h"
 
 namespace daisy {
 
@@ -49,13 +51,11 @@ __global__ void k_pack_triples(const int32_t *__restrict__ u, const int32_t *__r
 // coalesced read), the rows of FWD_SUB samples are in flight together, their two scores land in
 // lane x, and the loss epilogue (exp/log) is evaluated once per run with one sample per lane
 // instead of once per sample on a single lane.
+constexpr int kFwdSub = 4;      // samples whose rows are in flight together, at up to 4 floats per lane
 template <class C>
 struct FwdCfg {
     static constexpr int RUN = C::LPR;
-#ifndef DAISY_FWD_SUB
-#define DAISY_FWD_SUB 4
-#endif
-    static constexpr int SUB = (C::NE <= 4) ? DAISY_FWD_SUB : ((C::NE <= 8) ? 2 : 1);
+    static constexpr int SUB = (C::NE <= 4) ? kFwdSub : ((C::NE <= 8) ? 2 : 1);
 };
 
 template <class C, bool POINTWISE>
@@ -244,270 +244,6 @@ __global__ __launch_bounds__(kBlock) void k_item_grad_sorted(
         for (int k = 0; k < C::NE; ++k) acc.v[k] += fmaf(w2, qr.v[k], w1 * sgn(qr.v[k]));
         acc.store(gQ + (int64_t)r * d, lane, d);
         if (v.g_bi && lane == 0) v.g_bi[r] = csum;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// item gradient, throughput mode: segmented reduction over the item-sorted
-// entries (data term  sum_e c_e * p_u(e)  only; the regulariser share is added
-// by k_item_reg or folded into the commit kernel).
-// A workgroup takes a chunk of G*RUN consecutive entries, every lane group a
-// run of RUN of them: one load fetches the run's metadata (lane x <- entry x),
-// then all RUN row gathers are in flight together.  A segment (= all entries of
-// one item) that lies inside one run is summed in registers and stored straight
-// to gQ by its group (single owner, no atomics, no LDS).  Only segments that
-// cross a run boundary - at most one per boundary - go through an LDS
-// accumulator slot (slot s>0: the segment that starts in run s-1; slot 0: the
-// segment inherited from the previous chunk); after a barrier each used slot is
-// written once: plain store if the segment lies inside the chunk, fp32 atomics
-// only when it is shared with a neighbouring chunk (<= 2 rows per chunk).
-// ---------------------------------------------------------------------------
-template <class C, int RUN_OVERRIDE = 0>
-struct RunCfg {
-    // needs RUN <= LPR (lane x holds the metadata of entry x); RUN*NE row registers are live at once
-    static constexpr int RUN_BY_REGS = (C::NE <= 4) ? 16 : ((C::NE <= 8) ? 4 : 2);
-    static constexpr int RUN_AUTO = RUN_BY_REGS < C::LPR ? RUN_BY_REGS : C::LPR;
-    static constexpr int RUN = (RUN_OVERRIDE > 0 && RUN_OVERRIDE <= C::LPR) ? RUN_OVERRIDE : RUN_AUTO;
-    static constexpr int G = C::GROUPS_PER_BLOCK;
-    static constexpr int E = G * RUN;
-};
-
-// DET (bitwise reproducible, no atomics): a group does not add its run-crossing partial sums into the
-// slot but parks them (<= 2 per group: the segment it continues, the segment it hands on) and the
-// slot's finisher adds them in group order; segments shared with a neighbouring chunk leave the chunk
-// as edge records that k_item_edges chains in chunk order.  Same data movement, fixed summation order.
-struct ItemEdges {
-    float *vec;          // [2*nchunks][d]  partial gradient rows; [2c] head edge (inherited), [2c+1] tail edge
-    int32_t *item;       // [2*nchunks]     their item (-1: none)
-    float *b;            // [2*nchunks]     FM: partial coefficient sums
-    int32_t *whole;      // [nchunks]       the head edge's segment also runs on into the next chunk
-    const double *halt = nullptr;   // BatchView::halt of the step the records belong to
-};
-
-template <class C, int RUN_OVERRIDE = 0, bool DET = false, bool XH = false>      // XH: the gathered rows are bf16
-__global__ __launch_bounds__(kBlock) void k_item_grad_chunked(const float *__restrict__ P,
-                                                              const float2 *__restrict__ coef,
-                                                              BatchView v, int d,
-                                                              float *__restrict__ gQ, ItemEdges edges = ItemEdges{}) {
-    if (halted(v.halt)) return;
-    constexpr int G = RunCfg<C, RUN_OVERRIDE>::G, RUN = RunCfg<C, RUN_OVERRIDE>::RUN,
-                  E = RunCfg<C, RUN_OVERRIDE>::E;
-    constexpr int ROWF = C::NE * C::LPR;
-    __shared__ float slot_acc[DET ? 1 : (G + 1) * ROWF];
-    __shared__ float slot_b[G + 1];              // FM: sum of the coefficients (d loss / d i_bias)
-    __shared__ int slot_item[G + 1], slot_shared[G + 1];
-    __shared__ int run_first[G], run_last[G];
-    __shared__ float part_acc[DET ? 2 * G * ROWF : 1];     // DET: [group][head|tail] parked partial sums
-    __shared__ float part_b[DET ? 2 * G : 1];
-    __shared__ int part_slot[DET ? 2 * G : 1];             //      the slot each belongs to (-1: unused)
-
-    const int tid = threadIdx.x;
-    const int lane = tid % C::LPR;
-    const int group = tid / C::LPR;
-    const int64_t n = 2 * v.B;
-    const int64_t nchunks = (n + E - 1) / E;
-
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const int64_t c0 = chunk * E;
-        const int64_t t0 = c0 + (int64_t)group * RUN;
-        const int64_t t1 = (t0 + RUN < n) ? (t0 + RUN) : n;
-        const int cnt = (t0 < n) ? (int)(t1 - t0) : 0;       // entries of this run
-
-        // ---- hop 1: the run's metadata, lane x <- entry x; plus the entries just before and
-        // after the run (same address on every lane: one request)
-        // Every load is unconditional on a clamped address (n >= 1 here): a branch around a
-        // load makes the compiler drain vmcnt before it, which would serialise these requests
-        // into one memory round trip each.
-        const int64_t last = n - 1;
-        const int64_t il = (t0 + lane < n) ? (t0 + lane) : last;
-        const uint32_t k_me = v.ekey[il];
-        const uint2 su_me = v.esu[il];
-        const uint32_t k_prev = v.ekey[(t0 > 0) ? ((t0 - 1 < n) ? t0 - 1 : last) : 0];
-        const uint32_t k_next = v.ekey[(t1 < n) ? t1 : last];
-        const uint32_t k_cprev = v.ekey[(c0 > 0) ? c0 - 1 : 0];
-        const int32_t my_item = (lane < cnt) ? (int32_t)((k_me & v.imask) >> 1) : -1;
-        const uint2 my_su = (lane < cnt) ? su_me : make_uint2(0u, 0u);
-        const int32_t item_prev = (cnt > 0 && t0 > 0) ? (int32_t)((k_prev & v.imask) >> 1) : -1;
-        const int32_t item_next = (cnt > 0 && t1 < n) ? (int32_t)((k_next & v.imask) >> 1) : -1;
-        const int32_t chunk_prev_item = (c0 > 0) ? (int32_t)((k_cprev & v.imask) >> 1) : -1;
-        if constexpr (!DET) {
-            for (int e = tid; e < (G + 1) * ROWF; e += kBlock) slot_acc[e] = 0.f;
-        } else {
-            if (tid < 2 * G) part_slot[tid] = -1;
-        }
-        if (tid <= G) { slot_item[tid] = -1; slot_shared[tid] = 0; slot_b[tid] = 0.f; }
-        const int32_t item_first = group_bcast<C>(my_item, 0);
-        const int32_t item_last = __shfl(my_item, cnt > 0 ? cnt - 1 : 0, C::LPR);
-        if (lane == 0) {
-            run_first[group] = cnt > 0 ? item_first : -2;
-            run_last[group] = cnt > 0 ? item_last : -2;
-        }
-
-        // ---- hop 2: coefficient of entry `lane`, and all row gathers of the run
-        const float2 c2 = coef[su_me.x & ~kNegBit];
-        const float my_c = (lane < cnt) ? ((su_me.x & kNegBit) ? c2.y : c2.x) : 0.f;
-        Row<C> p[RUN];
-        if (__all(cnt == RUN)) {        // wave-uniform: every run of this wave is full
-#pragma unroll
-            for (int x = 0; x < RUN; ++x) {
-                const uint32_t ux = group_bcast<C>(my_su.y, x);
-                if constexpr (XH) p[x].load_bf16(reinterpret_cast<const uint16_t *>(P) + (int64_t)ux * d, lane, d);
-                else p[x].load(P + (int64_t)ux * d, lane, d);
-            }
-        } else {
-#pragma unroll
-            for (int x = 0; x < RUN; ++x) {
-                const uint32_t ux = group_bcast<C>(my_su.y, x);
-                if (x >= cnt) p[x].zero();
-                else if constexpr (XH) p[x].load_bf16(reinterpret_cast<const uint16_t *>(P) + (int64_t)ux * d, lane, d);
-                else p[x].load(P + (int64_t)ux * d, lane, d);
-            }
-        }
-        __syncthreads();
-
-        if (cnt > 0) {
-            const bool cont = (t0 > 0) && (item_prev == item_first);
-            int cur_slot = -1;                      // >= 0: the current segment began before this run
-            if (cont) {
-                if (group == 0) cur_slot = 0;       // inherited from the previous chunk
-                else {
-                    int gs = group - 1;
-                    while (gs > 0 && run_first[gs] == item_first && run_last[gs - 1] == item_first) --gs;
-                    // the segment holds the last entry of run gs; it began there unless run 0 is
-                    // all this item and the chunk itself continues the previous chunk
-                    const bool inherited = (gs == 0) && (run_first[0] == item_first) && (c0 > 0) &&
-                                           (chunk_prev_item == item_first);
-                    cur_slot = inherited ? 0 : gs + 1;
-                }
-            }
-            int32_t cur_item = item_first;
-            Row<C> acc;
-            acc.zero();
-            float accb = 0.f;
-            auto finish = [&](bool ends_here, bool to_next_chunk) {
-                if (cur_slot < 0 && ends_here) {    // interior: this group owns gQ[cur_item]
-                    acc.store(gQ + (int64_t)cur_item * d, lane, d);
-                    if (v.g_bi && lane == 0) v.g_bi[cur_item] = accb;
-                } else {                            // crosses a run boundary: LDS slot
-                    const int s = (cur_slot >= 0) ? cur_slot : group + 1;
-                    if constexpr (DET) {            // park it: head partial (continued segment) or tail partial
-                        const int q = group * 2 + ((cur_slot >= 0) ? 0 : 1);
-                        float *dst = part_acc + q * ROWF;
-#pragma unroll
-                        for (int k = 0; k < C::NE; ++k) dst[k * C::LPR + lane] = acc.v[k];
-                        if (lane == 0) {
-                            part_slot[q] = s;
-                            part_b[q] = accb;
-                            slot_item[s] = cur_item;
-                            if (to_next_chunk) slot_shared[s] = 1;
-                        }
-                    } else {
-                        float *dst = slot_acc + s * ROWF;
-#pragma unroll
-                        for (int k = 0; k < C::NE; ++k) atomicAdd(dst + k * C::LPR + lane, acc.v[k]);
-                        if (lane == 0) {
-                            slot_item[s] = cur_item;
-                            atomicAdd(&slot_b[s], accb);
-                            if (to_next_chunk) slot_shared[s] = 1;
-                        }
-                    }
-                }
-            };
-#pragma unroll
-            for (int x = 0; x < RUN; ++x) {
-                if (x < cnt) {
-                    const int32_t it = group_bcast<C>(my_item, x);
-                    const float cx = group_bcast<C>(my_c, x);
-                    if (it != cur_item) {           // previous segment ended inside this run
-                        finish(true, false);
-                        cur_item = it;
-                        cur_slot = -1;
-                        acc.zero();
-                        accb = 0.f;
-                    }
-#pragma unroll
-                    for (int k = 0; k < C::NE; ++k) acc.v[k] = fmaf(cx, p[x].v[k], acc.v[k]);
-                    accb += cx;
-                }
-            }
-            const bool continues = (t1 < n) && (item_next == cur_item);
-            finish(!continues, continues && (group == G - 1));
-        }
-        __syncthreads();
-
-        if constexpr (DET) {
-            if (tid == 0) { edges.item[2 * chunk] = -1; edges.item[2 * chunk + 1] = -1; edges.whole[chunk] = 0; }
-            __syncthreads();
-        }
-        // one write per used slot (G+1 slots over G groups)
-        for (int s = group; s <= G; s += G) {
-            const int r = slot_item[s];
-            if (r < 0) continue;
-            Row<C> g;
-            if constexpr (DET) {                    // the parked partials of this slot, in group order
-                g.zero();
-                float gb = 0.f;
-                for (int q = 0; q < 2 * G; ++q) {
-                    if (part_slot[q] != s) continue;
-                    const float *src = part_acc + q * ROWF;
-#pragma unroll
-                    for (int k = 0; k < C::NE; ++k) g.v[k] += src[k * C::LPR + lane];
-                    gb += part_b[q];
-                }
-                const bool from_prev = (s == 0), to_next = slot_shared[s] != 0;
-                if (from_prev || to_next) {
-                    const int64_t e = 2 * chunk + (from_prev ? 0 : 1);
-                    g.store(edges.vec + e * d, lane, d);
-                    if (lane == 0) {
-                        edges.item[e] = r;
-                        edges.b[e] = gb;
-                        if (from_prev && to_next) edges.whole[chunk] = 1;
-                    }
-                } else {
-                    g.store(gQ + (int64_t)r * d, lane, d);
-                    if (v.g_bi && lane == 0) v.g_bi[r] = gb;
-                }
-                continue;
-            }
-            const float *src = slot_acc + s * ROWF;
-#pragma unroll
-            for (int k = 0; k < C::NE; ++k) g.v[k] = src[k * C::LPR + lane];
-            if (s == 0 || slot_shared[s]) {
-                g.atomic_add_to(gQ + (int64_t)r * d, lane, d);
-                if (v.g_bi && lane == 0) unsafeAtomicAdd(v.g_bi + r, slot_b[s]);
-            } else {
-                g.store(gQ + (int64_t)r * d, lane, d);
-                if (v.g_bi && lane == 0) v.g_bi[r] = slot_b[s];
-            }
-        }
-        __syncthreads();   // the slots are reused by the next chunk
-    }
-}
-
-// DET: chains of edge records - the chunk whose TAIL edge starts a segment owns it and adds the head edges
-// of the chunks it runs through, in chunk order (single writer per row, fixed order)
-template <class C>
-__global__ __launch_bounds__(kBlock) void k_item_edges(ItemEdges edges, int64_t nchunks, int d,
-                                                       float *__restrict__ gQ, float *__restrict__ g_bi) {
-    if (halted(edges.halt)) return;
-    const int lane = threadIdx.x % C::LPR;
-    const int group = threadIdx.x / C::LPR;
-    const int64_t gstride = (int64_t)gridDim.x * C::GROUPS_PER_BLOCK;
-    for (int64_t c = (int64_t)blockIdx.x * C::GROUPS_PER_BLOCK + group; c < nchunks; c += gstride) {
-        const int it = edges.item[2 * c + 1];
-        if (it < 0) continue;
-        Row<C> acc, t;
-        acc.load(edges.vec + (2 * c + 1) * d, lane, d);
-        float sb = edges.b[2 * c + 1];
-        for (int64_t k = c + 1; k < nchunks && edges.item[2 * k] == it; ++k) {
-            t.load(edges.vec + (2 * k) * d, lane, d);
-#pragma unroll
-            for (int q = 0; q < C::NE; ++q) acc.v[q] += t.v[q];
-            sb += edges.b[2 * k];
-            if (!edges.whole[k]) break;
-        }
-        acc.store(gQ + (int64_t)it * d, lane, d);
-        if (g_bi && lane == 0) g_bi[it] = sb;
     }
 }
 
@@ -912,79 +648,6 @@ __global__ __launch_bounds__(kBlock) void k_user_edges(float *__restrict__ P, in
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Dense Adam without touching every row in every step.  torch's Adam moves every element in every step (the moments
-// decay without a gradient), which at table sizes beyond the batch is most of the step's traffic.  But a row's
-// update sequence depends on nothing but its own gradients: a row without gradient in steps a+1..b can be brought
-// from its state after step a to its state after step b in registers (b - a zero-gradient updates, the very
-// expressions of k_adam_dense, dense_opt.hip, with g = 0) whenever it is next needed - before the step that reads it, or at a flush.
-// last[r] = the step row r has been updated to.  table[s] = (lr / (1 - beta1^s), sqrt(1 - beta2^s)) as the dense
-// entry point computes them on the host, so the replay uses the same bits.  Result: identical to daisy_adam_dense
-// in every step (tested bit for bit), HBM traffic proportional to the rows a step touches.
-// ---------------------------------------------------------------------------------------------------------
-struct AdamTable { float *W, *g, *m, *v; int32_t *last; };
-struct AdamHyper { const float2 *table; float beta1, beta2, eps; int32_t t; };
-
-// the lane group that raises last[row] from below `upto` wins the row: it replays the zero-gradient steps
-// last+1 .. upto-1 (catch-up, WITH_G = false: upto = t, the row is then current for step t's forward) or applies step
-// t itself with the row's gradient and clears it (WITH_G: upto = t + 1)
-template <class C, bool WITH_G>
-__device__ __forceinline__ void adam_claim_row(const AdamTable &T, int64_t row, int d, const AdamHyper &h, int lane) {
-    const int32_t target = WITH_G ? h.t : h.t - 1;
-    int32_t old = 0;
-    if (lane == 0) old = atomicMax(T.last + row, target);
-    old = group_bcast<C>(old, 0);
-    if (old >= target) return;
-    Row<C> w, m, v, g;
-    w.load(T.W + row * d, lane, d); m.load(T.m + row * d, lane, d); v.load(T.v + row * d, lane, d);
-    g.zero();
-    for (int32_t s = old + 1; s < (WITH_G ? h.t : h.t); ++s) {           // zero-gradient steps old+1 .. t-1
-        const float2 c = h.table[s];
-        adam_row<C>(w, m, v, g, c.x, c.y, h.beta1, h.beta2, h.eps);
-    }
-    if constexpr (WITH_G) {
-        g.load(T.g + row * d, lane, d);
-        const float2 c = h.table[h.t];
-        adam_row<C>(w, m, v, g, c.x, c.y, h.beta1, h.beta2, h.eps);
-        g.zero();
-        g.store(T.g + row * d, lane, d);
-    }
-    w.store(T.W + row * d, lane, d); m.store(T.m + row * d, lane, d); v.store(T.v + row * d, lane, d);
-}
-
-// every row reference of the current batch: user of sample s, its item(s)
-template <class C, bool WITH_G>
-__global__ __launch_bounds__(kBlock) void k_adam_batch_rows(BatchView v, int d, AdamTable TP, AdamTable TQ, AdamHyper h) {
-    const int lane = threadIdx.x % C::LPR, group = threadIdx.x / C::LPR;
-    const int64_t gstride = (int64_t)gridDim.x * C::GROUPS_PER_BLOCK;
-    for (int64_t s = (int64_t)blockIdx.x * C::GROUPS_PER_BLOCK + group; s < v.B; s += gstride) {
-        const int2 ij = v.ij[s];
-        adam_claim_row<C, WITH_G>(TP, (int64_t)(v.ukey[s] & v.umask), d, h, lane);
-        adam_claim_row<C, WITH_G>(TQ, (int64_t)ij.x, d, h, lane);
-        if (!v.pointwise) adam_claim_row<C, WITH_G>(TQ, (int64_t)ij.y, d, h, lane);
-    }
-}
-
-// all rows up to step t (end of an epoch, before the tables are read by anything but a step)
-template <class C>
-__global__ __launch_bounds__(kBlock) void k_adam_flush(AdamTable T, int64_t rows, int d, AdamHyper h) {
-    const int lane = threadIdx.x % C::LPR, group = threadIdx.x / C::LPR;
-    const int64_t gstride = (int64_t)gridDim.x * C::GROUPS_PER_BLOCK;
-    for (int64_t r = (int64_t)blockIdx.x * C::GROUPS_PER_BLOCK + group; r < rows; r += gstride) {
-        const int32_t old = T.last[r];
-        if (old >= h.t) continue;
-        Row<C> w, m, v, g;
-        w.load(T.W + r * d, lane, d); m.load(T.m + r * d, lane, d); v.load(T.v + r * d, lane, d);
-        g.zero();
-        for (int32_t s = old + 1; s <= h.t; ++s) {
-            const float2 c = h.table[s];
-            adam_row<C>(w, m, v, g, c.x, c.y, h.beta1, h.beta2, h.eps);
-        }
-        w.store(T.W + r * d, lane, d); m.store(T.m + r * d, lane, d); v.store(T.v + r * d, lane, d);
-        if (lane == 0) T.last[r] = h.t;
-    }
-}
-
 int launch_reduce_partials(const double *partials, int nblocks, double *stats, bool finalize, float reg_1,
                            float reg_2, double *epoch_acc, double *step_loss, hipStream_t s) {
     if (finalize)
@@ -1001,59 +664,40 @@ int launch_reduce_partials(const double *partials, int nblocks, double *stats, b
 
 using namespace daisy;
 
-// out[row] = sum over the row's entries of coef[e].x * X[col_e]  (a sparse-matrix x dense-matrix product
-// for entries sorted by row): the item pass's segmented reduction (bitwise reproducible variant) on a
-// synthetic view - ekey[e] = row << 1, esu[e] = (e, col), coef[e] = (value, 0).  Rows without entries are
-// not written; n_entries must be even.  `edges` is scratch for segsum_chunks(n_entries, d) chunks.
-namespace daisy {
-int64_t segsum_chunks(int64_t n_entries, int d) {
-    int64_t nchunks = 0;
-    (void)dispatch_d(d, [&](auto cfg) {
-        using C = decltype(cfg);
-        nchunks = (n_entries + RunCfg<C>::E - 1) / RunCfg<C>::E;
-        return DAISY_OK;
-    });
-    return nchunks;
-}
-
-int segsum_rows(const float *X, const float2 *coef, const uint32_t *ekey, const uint2 *esu, int64_t n_entries,
-                int d, float *out, float *edge_vec, int32_t *edge_item, float *edge_b, int32_t *edge_whole,
-                hipStream_t s, bool x_bf16) {
-    if (n_entries <= 0) return DAISY_OK;
-    if (n_entries & 1) { set_error("segsum_rows: odd entry count %lld", (long long)n_entries); return DAISY_ERR_ARG; }
-    BatchView v{};
-    v.ekey = ekey;
-    v.esu = esu;
-    v.imask = 0xFFFFFFFFu;
-    v.B = n_entries / 2;
-    ItemEdges ed{edge_vec, edge_item, edge_b, edge_whole};
-    static const int tune_run = getenv("DAISY_SEGSUM_RUN") ? atoi(getenv("DAISY_SEGSUM_RUN")) : 4;
-    int rc = dispatch_d(d, [&](auto cfg) {
-        using C = decltype(cfg);
-        auto go = [&](auto ro_tag) {
-            // wide rows (d > 128: 16 floats per lane) default to 2 rows in flight per lane group; 4 measured faster
-            // for the NeuMF tables (fewer, longer chunks: 3 barriers per chunk)
-            constexpr int RO = decltype(ro_tag)::value;
-            const int64_t nchunks = (n_entries + RunCfg<C, RO>::E - 1) / RunCfg<C, RO>::E;
-            const dim3 g(grid_for(n_entries, RunCfg<C, RO>::E, 16384)), ge(grid_for(nchunks, C::GROUPS_PER_BLOCK));
-            if (x_bf16) hipLaunchKernelGGL((k_item_grad_chunked<C, RO, true, true>), g, dim3(kBlock), 0, s, X, coef, v, d, out, ed);
-            else hipLaunchKernelGGL((k_item_grad_chunked<C, RO, true>), g, dim3(kBlock), 0, s, X, coef, v, d, out, ed);
-            hipLaunchKernelGGL((k_item_edges<C>), ge, dim3(kBlock), 0, s, ed, nchunks, d, out, (float *)nullptr);
-        };
-        if (C::NE == 16 && tune_run == 4) go(std::integral_constant<int, 4>{});
-        else go(std::integral_constant<int, 0>{});
-        return DAISY_OK;
-    });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-}  // namespace daisy
-
 static void view_bias(daisy_bpr_ctx *ctx) {
     BatchView &v = ctx->v;
     v.bu = ctx->bu; v.bi = ctx->bi; v.b0 = ctx->b0;
     v.g_bu = ctx->g_bu; v.g_bi = ctx->g_bi; v.g_b0 = ctx->g_b0;
+}
+
+// the context's current batch: a batch of the sorted plan layout, which every phase reads
+static void adopt_sorted_batch(daisy_bpr_ctx *ctx, const BatchView &v) {
+    ctx->v = v;
+    ctx->sv = stream_view_of(ctx->v);
+    ctx->batch_kind = 0;
+    view_bias(ctx);
+    ctx->cur_plan = nullptr;
+    ctx->batch_set = true; ctx->fwd_done = false; ctx->n_slices = 0;
+}
+
+// a phase that reads the sorted layout, called on a batch of a partitioned plan
+static int partitioned_batch_error(const char *who) {
+    set_error("%s: the current batch comes from a partitioned plan (daisy_epoch_plan_build_indexed), which only "
+              "daisy_bpr_sgd_step / daisy_bpr_fit_epoch_sgd with DAISY_ITEM_FUSED and the daisy_bpr_staged_* phases read", who);
+    return DAISY_ERR_STATE;
+}
+
+static int launch_item_reg(daisy_bpr_ctx *ctx, const float *Q, const double *stats, float reg_1, float reg_2,
+                           float *gQ, hipStream_t s) {
+    const BatchView &v = ctx->v;
+    return dispatch_d(ctx->d, [&](auto cfg) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL((k_item_reg<C>),
+                           dim3(grid_for(2 * v.B < ctx->I ? 2 * v.B : ctx->I, C::GROUPS_PER_BLOCK * 2)),
+                           dim3(kBlock), 0, s, Q, v, ctx->d, stats, reg_1, reg_2, gQ);
+        DAISY_LAUNCH_CHECK();
+        return DAISY_OK;
+    });
 }
 
 // =============================================================================
@@ -1091,10 +735,10 @@ int daisy_bpr_ctx_create(daisy_bpr_ctx **out, int64_t max_batch, int32_t d, int6
     a.add(&c->tmp_triples, (size_t)max_batch * 12);
     // edge records: two per chunk of the user pass (B samples) or of the item pass (2B entries)
     size_t max_chunks = 0, chunks2 = 0;
+    const size_t ci = (size_t)segsum_chunks(2 * max_batch, d);
     (void)dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         const size_t cu = ((size_t)max_batch + UserRunCfg<C>::E - 1) / UserRunCfg<C>::E;
-        const size_t ci = (2 * (size_t)max_batch + RunCfg<C>::E - 1) / RunCfg<C>::E;
         // staged passes (bpr_staged.h): the sparse flavour of the item pass has its smallest chunks, over 2 B entries, and
         // the user pass's B samples never make more chunks than that
         using Sparse = StagedItemCfg<C, kStagedItemBlock, true>;
@@ -1202,14 +846,10 @@ int daisy_bpr_set_batch_from_plan(daisy_bpr_ctx *ctx, const daisy_epoch_plan *pl
         ctx->v.B = ctx->sv.B;
         ctx->batch_kind = 1;
         ctx->cur_plan = plan; ctx->cur_k = k; ctx->cur_gen = plan->build_gen;
+        ctx->batch_set = true; ctx->fwd_done = false; ctx->n_slices = 0;
     } else {
-        ctx->v = plan_view(plan, k);
-        ctx->sv = stream_view_of(ctx->v);
-        ctx->batch_kind = 0;
-        view_bias(ctx);
-        ctx->cur_plan = nullptr;
+        adopt_sorted_batch(ctx, plan_view(plan, k));
     }
-    ctx->batch_set = true; ctx->fwd_done = false; ctx->n_slices = 0;
     return DAISY_OK;
 }
 
@@ -1228,12 +868,7 @@ int daisy_bpr_set_batch_from_triples(daisy_bpr_ctx *ctx, const int32_t *triples,
     rc = plan_build(ctx->own_plan, triples, B, idx ? 0 : start, idx, idx ? DAISY_ORDER_PERM : DAISY_ORDER_IDENTITY,
                     0, 0, B, user_base, ctx->pointwise ? DAISY_PLAN_POINTWISE : 0, as_stream(stream), idx ? n_triples : -1);
     if (rc) return rc;
-    ctx->v = plan_view(ctx->own_plan, 0);
-    ctx->sv = stream_view_of(ctx->v);
-    ctx->batch_kind = 0;
-    view_bias(ctx);
-    ctx->cur_plan = nullptr;
-    ctx->batch_set = true; ctx->fwd_done = false; ctx->n_slices = 0;
+    adopt_sorted_batch(ctx, plan_view(ctx->own_plan, 0));
     return DAISY_OK;
 }
 
@@ -1256,11 +891,7 @@ static int forward_impl(daisy_bpr_ctx *ctx, const float *P, const float *Q, int3
     DAISY_CHECK_ARG(loss_type >= DAISY_LOSS_BPR && loss_type <= DAISY_LOSS_SL,
                     "Invalid loss type: %d", loss_type);
     if (!ctx->batch_set) { set_error("forward: no batch set"); return DAISY_ERR_STATE; }
-    if (ctx->batch_kind != 0) {
-        set_error("%s: the current batch comes from a partitioned plan (daisy_epoch_plan_build_indexed), which only "
-                  "daisy_bpr_sgd_step / daisy_bpr_fit_epoch_sgd with DAISY_ITEM_FUSED and the daisy_bpr_staged_* phases read", "forward");
-        return DAISY_ERR_STATE;
-    }
+    if (ctx->batch_kind != 0) return partitioned_batch_error("forward");
     DAISY_CHECK_ARG((loss_type >= DAISY_LOSS_CL) == (ctx->v.pointwise != 0),
                     "forward: loss type %d does not match the batch layout (point-wise=%d)", loss_type,
                     ctx->v.pointwise);
@@ -1281,13 +912,8 @@ static int forward_impl(daisy_bpr_ctx *ctx, const float *P, const float *Q, int3
     });
     if (rc) return rc;
     DAISY_LAUNCH_CHECK();
-    if (finalize)
-        hipLaunchKernelGGL((k_reduce_partials<true>), dim3(1), dim3(kBlock), 0, s, ctx->partials, grid,
-                           stats, reg_1, reg_2, epoch_acc, step_loss);
-    else
-        hipLaunchKernelGGL((k_reduce_partials<false>), dim3(1), dim3(kBlock), 0, s, ctx->partials, grid,
-                           stats, 0.f, 0.f, nullptr, nullptr);
-    DAISY_LAUNCH_CHECK();
+    if ((rc = launch_reduce_partials(ctx->partials, grid, stats, finalize, reg_1, reg_2, epoch_acc, step_loss, s)))
+        return rc;
     ctx->fwd_done = true;
     return DAISY_OK;
 }
@@ -1319,53 +945,27 @@ static int item_grad_impl(daisy_bpr_ctx *ctx, const float *P, const float *Q, co
     const BatchView &v = ctx->v;
     const int d = ctx->d;
     const bool reg = (reg_1 != 0.f) || (reg_2 != 0.f);
-    int rc = dispatch_d(d, [&](auto cfg) {
+    if (item_mode == DAISY_ITEM_CHUNKED) {
+        // the user pass has not run yet: its edge records serve the item entries first
+        const ItemEdges ed{ctx->edge_vec, ctx->edge_user, ctx->edge_n, ctx->edge_whole};
+        if (int rc = segsum_item_grad(v, P, ctx->coef, d, gQ, ed, v.g_bi, s)) return rc;
+        return (reg && !data_only) ? launch_item_reg(ctx, Q, stats, reg_1, reg_2, gQ, s) : DAISY_OK;
+    }
+    return dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
-        if (item_mode == DAISY_ITEM_SORTED) {
+        if (item_mode == DAISY_ITEM_SORTED)
             hipLaunchKernelGGL((k_item_grad_sorted<C>),
                                dim3(grid_for(2 * v.B, C::GROUPS_PER_BLOCK, kMaxGridSparse)), dim3(kBlock), 0,
                                s, P, Q, ctx->coef, v, d, stats, reg_1, reg_2, gQ);
-        } else if (item_mode == DAISY_ITEM_CHUNKED) {
-            static const int tune_run = getenv("DAISY_CHUNK_RUN") ? atoi(getenv("DAISY_CHUNK_RUN")) : 0;
-            static const int tune_cap = getenv("DAISY_CHUNK_GRID") ? atoi(getenv("DAISY_CHUNK_GRID")) : 16384;
-            // 1 (default): bitwise reproducible variant (parked partials + edge records); 0: the variant that
-            // combines shared segments with fp32 atomics (kept for A/B measurements)
-            static const int tune_det = getenv("DAISY_ITEM_DET") ? atoi(getenv("DAISY_ITEM_DET")) : 1;
-            if (tune_run == 4)
-                hipLaunchKernelGGL((k_item_grad_chunked<C, 4>), dim3(grid_for(2 * v.B, RunCfg<C, 4>::E, tune_cap)),
-                                   dim3(kBlock), 0, s, P, ctx->coef, v, d, gQ);
-            else if (tune_run == 16)
-                hipLaunchKernelGGL((k_item_grad_chunked<C, 16>), dim3(grid_for(2 * v.B, RunCfg<C, 16>::E, tune_cap)),
-                                   dim3(kBlock), 0, s, P, ctx->coef, v, d, gQ);
-            else if (tune_run == 12)
-                hipLaunchKernelGGL((k_item_grad_chunked<C, 12>), dim3(grid_for(2 * v.B, RunCfg<C, 12>::E, tune_cap)),
-                                   dim3(kBlock), 0, s, P, ctx->coef, v, d, gQ);
-            else if (tune_det) {
-                const int64_t nchunks = (2 * v.B + RunCfg<C>::E - 1) / RunCfg<C>::E;
-                ItemEdges ed{ctx->edge_vec, ctx->edge_user, ctx->edge_n, ctx->edge_whole, v.halt};
-                hipLaunchKernelGGL((k_item_grad_chunked<C, 0, true>), dim3(grid_for(2 * v.B, RunCfg<C>::E, tune_cap)),
-                                   dim3(kBlock), 0, s, P, ctx->coef, v, d, gQ, ed);
-                hipLaunchKernelGGL((k_item_edges<C>), dim3(grid_for(nchunks, C::GROUPS_PER_BLOCK)), dim3(kBlock), 0, s,
-                                   ed, nchunks, d, gQ, v.g_bi);
-            } else
-                hipLaunchKernelGGL((k_item_grad_chunked<C>), dim3(grid_for(2 * v.B, RunCfg<C>::E, tune_cap)),
-                                   dim3(kBlock), 0, s, P, ctx->coef, v, d, gQ);
-            if (reg && !data_only)
-                hipLaunchKernelGGL((k_item_reg<C>),
-                                   dim3(grid_for(2 * v.B < ctx->I ? 2 * v.B : ctx->I, C::GROUPS_PER_BLOCK * 2)),
-                                   dim3(kBlock), 0, s, Q, v, d, stats, reg_1, reg_2, gQ);
-        } else if (reg) {
+        else if (reg)
             hipLaunchKernelGGL((k_item_grad_atomic<C, true>), dim3(grid_for(v.B, C::GROUPS_PER_BLOCK * 4)),
                                dim3(kBlock), 0, s, P, Q, v, ctx->coef, d, stats, reg_1, reg_2, gQ);
-        } else {
+        else
             hipLaunchKernelGGL((k_item_grad_atomic<C, false>), dim3(grid_for(v.B, C::GROUPS_PER_BLOCK * 4)),
                                dim3(kBlock), 0, s, P, Q, v, ctx->coef, d, stats, reg_1, reg_2, gQ);
-        }
+        DAISY_LAUNCH_CHECK();
         return DAISY_OK;
     });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
 }
 
 int daisy_bpr_item_grad(daisy_bpr_ctx *ctx, const float *P, const float *Q, const double *stats,
@@ -1386,24 +986,9 @@ int daisy_bpr_item_grad_reg(daisy_bpr_ctx *ctx, const float *Q, const double *st
                             float reg_2, float *gQ, daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && Q && stats && gQ, "item_grad_reg: NULL argument");
     if (!ctx->batch_set) { set_error("item_grad_reg: no batch set"); return DAISY_ERR_STATE; }
-    if (ctx->batch_kind != 0) {
-        set_error("%s: the current batch comes from a partitioned plan (daisy_epoch_plan_build_indexed), which only "
-                  "daisy_bpr_sgd_step / daisy_bpr_fit_epoch_sgd with DAISY_ITEM_FUSED and the daisy_bpr_staged_* phases read", "item_grad_reg");
-        return DAISY_ERR_STATE;
-    }
+    if (ctx->batch_kind != 0) return partitioned_batch_error("item_grad_reg");
     if (reg_1 == 0.f && reg_2 == 0.f) return DAISY_OK;
-    const BatchView &v = ctx->v;
-    const int d = ctx->d;
-    int rc = dispatch_d(d, [&](auto cfg) {
-        using C = decltype(cfg);
-        hipLaunchKernelGGL((k_item_reg<C>),
-                           dim3(grid_for(2 * v.B < ctx->I ? 2 * v.B : ctx->I, C::GROUPS_PER_BLOCK * 2)),
-                           dim3(kBlock), 0, as_stream(stream), Q, v, d, stats, reg_1, reg_2, gQ);
-        return DAISY_OK;
-    });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
+    return launch_item_reg(ctx, Q, stats, reg_1, reg_2, gQ, as_stream(stream));
 }
 
 static int user_pass(daisy_bpr_ctx *ctx, float *P, const float *Q, const double *stats, float lr,
@@ -1415,11 +1000,10 @@ static int user_pass(daisy_bpr_ctx *ctx, float *P, const float *Q, const double 
     hipStream_t s = as_stream(stream);
     const BatchView &v = ctx->v;
     const int d = ctx->d;
-    static const int user_kernel = getenv("DAISY_USER_KERNEL") ? atoi(getenv("DAISY_USER_KERNEL")) : 1;
-    int rc = dispatch_d(d, [&](auto cfg) {
+    return dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         const int grid = grid_for(v.B, C::GROUPS_PER_BLOCK * 2);
-        if (sgd && chunked && user_kernel == 1 && C::NE <= 4) {
+        if (sgd && chunked && C::NE <= 4) {
             const int64_t nchunks = (v.B + UserRunCfg<C>::E - 1) / UserRunCfg<C>::E;
             hipLaunchKernelGGL((k_user_chunked<C>), dim3(grid_for(nchunks, 1, 16384)), dim3(kBlock), 0,
                                s, P, Q, v, ctx->coef, d, stats, lr, reg_1, reg_2, ctx->edge_vec,
@@ -1438,11 +1022,9 @@ static int user_pass(daisy_bpr_ctx *ctx, float *P, const float *Q, const double 
             hipLaunchKernelGGL((k_user<C, false>), dim3(grid), dim3(kBlock), 0, s, P, Q, v, ctx->coef, d,
                                stats, lr, reg_1, reg_2, gP);
         }
+        DAISY_LAUNCH_CHECK();
         return DAISY_OK;
     });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
 }
 
 int daisy_bpr_user_sgd(daisy_bpr_ctx *ctx, float *P, const float *Q, const double *stats, float lr,
@@ -1465,15 +1047,12 @@ static int item_apply_impl(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, in
                            daisy_stream_t stream) {
     DAISY_CHECK_ARG(ctx && Q && gQ, "item_sgd_apply: NULL argument");
     if (!dense && !ctx->batch_set) { set_error("item_sgd_apply: no batch set"); return DAISY_ERR_STATE; }
-    if (!dense && ctx->batch_kind != 0) {
-        set_error("item_sgd_apply: the current batch comes from a partitioned plan; only dense != 0 applies there");
-        return DAISY_ERR_STATE;
-    }
+    if (!dense && ctx->batch_kind != 0) return partitioned_batch_error("item_sgd_apply with dense == 0");
     hipStream_t s = as_stream(stream);
     const int d = ctx->d;
     const BatchView &v = ctx->v;
     const int64_t n = dense ? ctx->I : (2 * v.B < ctx->I ? 2 * v.B : ctx->I);   // upper bound of rows
-    int rc = dispatch_d(d, [&](auto cfg) {
+    return dispatch_d(d, [&](auto cfg) {
         using C = decltype(cfg);
         const int grid = grid_for(n, C::GROUPS_PER_BLOCK * 2);
         if (with_reg)
@@ -1482,85 +1061,14 @@ static int item_apply_impl(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, in
         else
             hipLaunchKernelGGL((k_item_apply<C, false>), dim3(grid), dim3(kBlock), 0, s, Q, gQ, v, ctx->I, d,
                                lr, (int)dense, stats, reg_1, reg_2);
+        DAISY_LAUNCH_CHECK();
         return DAISY_OK;
     });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
 }
 
 int daisy_bpr_item_sgd_apply(daisy_bpr_ctx *ctx, float *Q, float *gQ, float lr, int32_t dense,
                              daisy_stream_t stream) {
     return item_apply_impl(ctx, Q, gQ, lr, dense, nullptr, 0.f, 0.f, false, stream);
-}
-
-int daisy_adam_lazy_table(float lr, float beta1, float beta2, int64_t n_steps, float *table_host) {
-    DAISY_CHECK_ARG(table_host && n_steps >= 1, "adam_lazy_table: bad argument");
-    table_host[0] = table_host[1] = 0.f;                              // step 0 does not exist
-    for (int64_t s = 1; s <= n_steps; ++s) {                          // the host arithmetic of daisy_adam_dense (dense_opt.hip)
-        const double bc1 = 1.0 - pow((double)beta1, (double)s), bc2 = 1.0 - pow((double)beta2, (double)s);
-        table_host[2 * s] = (float)((double)lr / bc1);
-        table_host[2 * s + 1] = (float)sqrt(bc2);
-    }
-    return DAISY_OK;
-}
-
-static int adam_lazy_batch(daisy_bpr_ctx *ctx, bool with_g, float *P, float *gP, float *mP, float *vP, int32_t *lastP,
-                           float *Q, float *gQ, float *mQ, float *vQ, int32_t *lastQ, const float *table, float beta1,
-                           float beta2, float eps, int64_t step, hipStream_t s) {
-    if (!ctx->batch_set || ctx->batch_kind != 0) {
-        set_error("adam_lazy: needs a batch of the sorted plan layout / daisy_bpr_set_batch*");
-        return DAISY_ERR_STATE;
-    }
-    // rows of P change behind the staged step's row-norm cache and behind a pre-norm that rode on its last item pass
-    // (a caller may hand the same LazyAdam state to this path and to daisy_bpr_staged_adam_step on one context)
-    ctx->p_sqnorm_of = nullptr;
-    ctx->pre_ready = false;
-    const BatchView &v = ctx->v;
-    const AdamTable TP{P, gP, mP, vP, lastP}, TQ{Q, gQ, mQ, vQ, lastQ};
-    const AdamHyper h{reinterpret_cast<const float2 *>(table), beta1, beta2, eps, (int32_t)step};
-    int rc = dispatch_d(ctx->d, [&](auto cfg) {
-        using C = decltype(cfg);
-        const dim3 g(grid_for(v.B, C::GROUPS_PER_BLOCK, 8192));
-        if (with_g) hipLaunchKernelGGL((k_adam_batch_rows<C, true>), g, dim3(kBlock), 0, s, v, ctx->d, TP, TQ, h);
-        else hipLaunchKernelGGL((k_adam_batch_rows<C, false>), g, dim3(kBlock), 0, s, v, ctx->d, TP, TQ, h);
-        return DAISY_OK;
-    });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
-}
-
-int daisy_adam_lazy_catchup(daisy_bpr_ctx *ctx, float *P, float *mP, float *vP, int32_t *lastP, float *Q, float *mQ,
-                            float *vQ, int32_t *lastQ, const float *table, float beta1, float beta2, float eps,
-                            int64_t step, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(ctx && P && mP && vP && lastP && Q && mQ && vQ && lastQ && table && step >= 1, "adam_lazy_catchup: bad argument");
-    return adam_lazy_batch(ctx, false, P, nullptr, mP, vP, lastP, Q, nullptr, mQ, vQ, lastQ, table, beta1, beta2, eps, step,
-                           as_stream(stream));
-}
-
-int daisy_adam_lazy_step(daisy_bpr_ctx *ctx, float *P, float *gP, float *mP, float *vP, int32_t *lastP, float *Q,
-                         float *gQ, float *mQ, float *vQ, int32_t *lastQ, const float *table, float beta1, float beta2,
-                         float eps, int64_t step, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(ctx && P && gP && mP && vP && lastP && Q && gQ && mQ && vQ && lastQ && table && step >= 1,
-                    "adam_lazy_step: bad argument");
-    return adam_lazy_batch(ctx, true, P, gP, mP, vP, lastP, Q, gQ, mQ, vQ, lastQ, table, beta1, beta2, eps, step, as_stream(stream));
-}
-
-int daisy_adam_lazy_flush(float *W, float *m, float *v, int32_t *last, int64_t rows, int32_t d, const float *table,
-                          float beta1, float beta2, float eps, int64_t step, daisy_stream_t stream) {
-    DAISY_CHECK_ARG(W && m && v && last && table && rows > 0 && step >= 0, "adam_lazy_flush: bad argument");
-    const AdamTable T{W, nullptr, m, v, last};
-    const AdamHyper h{reinterpret_cast<const float2 *>(table), beta1, beta2, eps, (int32_t)step};
-    int rc = dispatch_d(d, [&](auto cfg) {
-        using C = decltype(cfg);
-        hipLaunchKernelGGL((k_adam_flush<C>), dim3(grid_for(rows, C::GROUPS_PER_BLOCK * 2)), dim3(kBlock), 0, as_stream(stream), T,
-                           rows, (int)d, h);
-        return DAISY_OK;
-    });
-    if (rc) return rc;
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
 }
 
 int daisy_bpr_sgd_step(daisy_bpr_ctx *ctx, float *P, float *Q, int32_t loss_type, float gamma,

@@ -1,11 +1,12 @@
 // LightGCN (daisy/model/LightGCNRecommender.py) on gfx950: the normalised bipartite adjacency as a
 // row-sorted entry list on the device, the propagation out = mean_k A^k E0 and its transpose.
-// The sparse x dense products run on the item pass's segmented-reduction kernel (segsum_rows in
-// bpr_train.hip): random 256-byte row gathers, 16 rows in flight per lane group, single-owner
+// The sparse x dense products run on the library's segmented sum (segsum_rows, segsum.hip; its kernel is
+// k_item_grad_chunked): random 256-byte row gathers, 16 rows in flight per lane group, single-owner
 // stores - an HBM-bound kernel, no MFMA.  Everything else of a LightGCN step is the MF path.
 #include <stdlib.h>
 
 #include "common.h"
+#include "segsum.h"
 
 namespace daisy {
 

@@ -3,14 +3,15 @@
 // row has one owner that adds its rows' contributions in ascending row order, so two runs give the same bits.
 //   small steps (<= kScanMaxRows rows, fp32)   k_nmf_scatter_scan (or k_nmf_scatter_small), one launch
 //   otherwise, the owner chain                 rows grouped by table row (the counting pass k_cs_*, or two radix sorts), then
-//                                              per table a segmented reduction over the grouped list on the MF item pass's
-//                                              kernel (segsum_rows) and k_nmf_table_commit*: the regulariser terms are
+//                                              per table a segmented sum over the grouped list (segsum_rows, segsum.hip:
+//                                              k_item_grad_chunked) and k_nmf_table_commit*: the regulariser terms are
 //                                              count * f(row) per table row (integer counts)
 // (With ml-1m's 6040 users a batch of 524 288 rows hits every user row ~87 times: fp32 atomics serialise on those addresses.)
 #include <stdlib.h>
 
 #include "common.h"
 #include "neumf_internal.h"
+#include "segsum.h"
 
 namespace daisy {
 

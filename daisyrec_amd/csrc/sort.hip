@@ -1,7 +1,7 @@
 // rocPRIM (AMD's native device primitives) wrappers.  Only index preparation
 // goes through these radix sorts (grouping a batch by user / by item, the
 // epoch permutation, argsort of candidate scores); the gather / dot / update
-// kernels of the hot path are hand written (epoch_plan.hip, bpr_train.hip, bpr_staged_user.hip, bpr_staged_item.hip and the models' own files).
+// kernels of the hot path are hand written (epoch_plan.hip, bpr_train.hip, segsum.hip, adam_lazy.hip, bpr_staged_user.hip, bpr_staged_item.hip and the models' own files).
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>

@@ -498,7 +498,7 @@ class DenseOptimizer:
 class LazyAdam:
     """torch.optim.Adam (defaults) on the two MF tables with traffic proportional to the rows a step touches, and the
     same bits as the dense form: rows without a gradient are replayed in registers when next needed
-    (csrc/bpr_train.hip: k_adam_batch_rows / k_adam_flush).  Usage per step: `catchup(ctx)` before the forward
+    (csrc/adam_lazy.hip: k_adam_batch_rows / k_adam_flush).  Usage per step: `catchup(ctx)` before the forward
     pass, `step(ctx, gP, gQ)` after the gradients; `flush()` before anything else reads the tables."""
 
     BETA1, BETA2, EPS = 0.9, 0.999, 1e-8

@@ -45,9 +45,11 @@ def test_graph_is_the_reference_adjacency_and_spmm(kat_lg):
     graph.close()
 
 
-@pytest.mark.parametrize("U,I,n,d", [(3, 2, 7, 8), (2000, 10, 30000, 64), (50, 5000, 20001, 32), (300, 300, 1, 20)])
+@pytest.mark.parametrize("U,I,n,d", [(3, 2, 7, 8), (2000, 10, 30000, 64), (50, 5000, 20001, 32), (300, 300, 1, 20),
+                                     (3, 2, 7, 160), (2000, 10, 30000, 160), (50, 5000, 20001, 300)])
 def test_spmm_shapes_long_and_short_rows(U, I, n, d):
-    """few items -> item rows with thousands of neighbours (chunk-crossing segments), isolated nodes, d % 4 != 0"""
+    """few items -> item rows with thousands of neighbours (chunk-crossing segments), isolated nodes, d % 4 != 0; d > 128:
+    16 floats per lane, where the segmented sum (segsum_rows) takes runs of 4 entries instead of the shape's default 2"""
     from daisyrec_amd import ops
     rng = np.random.default_rng(n)
     gu, gi = rng.integers(0, U, n), rng.integers(0, I, n)

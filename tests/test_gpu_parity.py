@@ -647,17 +647,16 @@ def test_pointwise_cl_through_sampler_and_fit(ops, ml100k):
         ctx.forward(model.embed_user.weight.data, model.embed_item.weight.data, ops.LOSS_IDS["BPR"])
 
 
-def test_chunked_mode_is_bitwise_reproducible(ops):
-    """The throughput kernels leave no summation order to chance (parked partials added in group order,
-    edge records chained in chunk order, fixed-order batch sums): two runs give identical bits - on a batch
-    with hot users and hot items whose runs cross many chunks."""
+def _chunked_mode_reproducible(ops, U, I, d, B, min_hot_entries):
+    """three chunked steps, three times, on a batch where user 7 takes ~30 % of the samples and item 5 ~30 % of the
+    positives: bit-equal between the runs, and equal to the oracle's three steps"""
     rng = np.random.default_rng(3)
-    U, I, d, B = 5000, 300, 64, 60000
     P0 = (rng.standard_normal((U, d)) * 0.1).astype(np.float32)
     Q0 = (rng.standard_normal((I, d)) * 0.1).astype(np.float32)
-    u = np.where(rng.random(B) < 0.3, 7, rng.integers(0, U, B)).astype(np.int32)       # a user with ~18k samples
-    i = np.where(rng.random(B) < 0.3, 5, rng.integers(0, I, B)).astype(np.int32)       # an item with ~18k entries
+    u = np.where(rng.random(B) < 0.3, 7, rng.integers(0, U, B)).astype(np.int32)       # the hot user
+    i = np.where(rng.random(B) < 0.3, 5, rng.integers(0, I, B)).astype(np.int32)       # the hot item
     j = rng.integers(0, I, B).astype(np.int32)
+    assert int((i == 5).sum() + (j == 5).sum()) > min_hot_entries and int((u == 7).sum()) > min_hot_entries
     outs = []
     for rep in range(3):
         P, Q = _t(P0), _t(Q0)
@@ -674,9 +673,24 @@ def test_chunked_mode_is_bitwise_reproducible(ops):
     Pn, Qn = P0, Q0
     for _ in range(3):
         loss, Pn, Qn = O.mf_sgd_step(Pn, Qn, u, i, j, 1e-3, 1e-3, 1e-3)
+    assert np.isfinite(loss) and np.isfinite(Pn).all() and np.isfinite(Qn).all()
     assert abs(outs[0][0] - loss) <= 1e-5 * abs(loss)
     np.testing.assert_allclose(outs[0][1], Pn, atol=2e-5)
     np.testing.assert_allclose(outs[0][2], Qn, atol=2e-5)
+
+
+def test_chunked_mode_is_bitwise_reproducible(ops):
+    """The throughput kernels leave no summation order to chance (parked partials added in group order,
+    edge records chained in chunk order, fixed-order batch sums): two runs give identical bits - on a batch
+    with hot users and hot items whose runs cross many chunks (a user with ~18k samples, an item with ~18k entries)."""
+    _chunked_mode_reproducible(ops, U=5000, I=300, d=64, B=60000, min_hot_entries=15000)
+
+
+def test_chunked_mode_reproducible_wide_rows(ops):
+    """The same at d = 256, where a lane holds 16 floats, a lane group's run is 2 entries and a chunk 32: the hot item's
+    ~1 300 entries run through dozens of whole chunks, so nearly every chunk hands its one segment on through the edge
+    records.  The row shape alone decides the run length of the segmented sum (segsum.hip); this pins the wide shape."""
+    _chunked_mode_reproducible(ops, U=200, I=40, d=256, B=4000, min_hot_entries=32 * 24)
 
 
 def test_c2_scale_step_against_the_numpy_oracle(ops):
