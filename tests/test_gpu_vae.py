@@ -419,12 +419,14 @@ def test_fit_epoch_equals_the_step_replay(ml):
     assert a.update == 2 * nb and a._steps == 2 * nb
 
 
-@pytest.mark.parametrize("opt", ["sgd", "adam", "adagrad", "rmsprop"])
-def test_fit_epoch_equals_step_grads_plus_the_dense_optimiser(opt):
+@pytest.mark.parametrize("opt,width", [pytest.param(o, w, id=o if w == 8 else f"{o}-width{w}") for w in (8, 6)
+                                       for o in ("sgd", "adam", "adagrad", "rmsprop")])
+def test_fit_epoch_equals_step_grads_plus_the_dense_optimiser(opt, width):
     """daisy_vae_fit_epoch against daisy_vae_step_grads + daisy_{sgd,adam,adagrad,rmsprop}_dense issued step by step:
     the flat parameters and the optimiser state bit for bit.  12 users x 40 items in batches of 5 (three steps, the last
-    one of 2 users), hidden [8], latent 4, the anneal still rising; the optimiser starts at step 5 and the noise at step
-    9, so a loop that fed Adam the wrong counter would show in the bias correction."""
+    one of 2 users), hidden [8] (the float4 entry kernels) or [6] (the scalar ones: the library-issued epoch runs
+    k_vae_enc0 / k_vae_w0grad too), latent 4, the anneal still rising; the optimiser starts at step 5 and the noise at
+    step 9, so a loop that fed Adam the wrong counter would show in the bias correction."""
     from daisyrec_amd import ops
     from daisyrec_amd import _native as N
     from daisyrec_amd.model import VAECF
@@ -441,7 +443,7 @@ def test_fit_epoch_equals_step_grads_plus_the_dense_optimiser(opt):
 
     def run(native):
         torch.manual_seed(2)
-        m = VAECF(vae_config(user_num=U, item_num=I, mlp_hidden_size=[8], latent_dim=4, dropout=0.0, lr=0.01, seed=7,
+        m = VAECF(vae_config(user_num=U, item_num=I, mlp_hidden_size=[width], latent_dim=4, dropout=0.0, lr=0.01, seed=7,
                              anneal_cap=cap, total_anneal_steps=total, history_item_id=torch.from_numpy(hid),
                              history_item_value=torch.from_numpy(hval)))
         W = m._params()

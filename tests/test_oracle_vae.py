@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import vae_cases as VC
 import vae_oracle as VO
 from conftest import mf_config
 
@@ -80,7 +81,7 @@ def test_rating_rows_match_reference(kat, case):
     m = kat_model(kat, case)
     for k in range(int(kat[f"{case}/meta"][4])):
         R = m.get_user_rating_matrix(torch.from_numpy(kat[f"{case}/users"][k]))
-        np.testing.assert_array_equal(R.numpy(), kat[f"{case}/R"][k])
+        np.testing.assert_array_equal(R.cpu().numpy(), kat[f"{case}/R"][k])
     hid = kat[f"{case}/hist_id"]
     assert (hid[1] == 0).sum() > 1 and hid[3].min() >= 0                  # user 1: item 0 and padding
     R0 = m.get_user_rating_matrix(torch.tensor([1, 2, 3]))
@@ -100,7 +101,7 @@ def test_history_csr_matches_rating_rows(kat):
             lo, hi = int(rp[u]), int(rp[u + 1])
             assert bool((col[lo + 1:hi] > col[lo:hi - 1]).all())          # items ascending within a row
             dense[u, col[lo:hi].long()] = val[lo:hi]
-        np.testing.assert_array_equal(dense.numpy(), R.numpy())
+        np.testing.assert_array_equal(dense.numpy(), R.cpu().numpy())
         assert bool((val != 0).all())
 
 
@@ -133,3 +134,68 @@ def test_ml100k_golden_is_consistent():
                                                        ml["ml/batch_losses"][per_epoch:].sum()], rtol=1e-6)
     for k in range(nb):
         assert ml[f"ml/eps{k}"].shape == (ml[f"ml/users{k}"].size, lat // 2)
+
+
+@pytest.mark.parametrize("name", VC.NAMES)
+def test_edge_cases_hold_their_promises_and_the_fp32_restatement_agrees(name):
+    """tests/vae_cases.py before any device sees it: every case has the structure its kernel path needs, the model's
+    rating rows and CSR of its history arrays are its R (item 0 stays out, so the padding rule changes nothing), and the
+    oracle's code run in torch.float32 - the reference's own arithmetic - holds the bounds the kernels are held to
+    (loss 1e-5 relative, every gradient 1e-5 of its tensor's largest element)."""
+    from daisyrec_amd import ops
+    from daisyrec_amd.model import VAECF
+    c = VC.case(name)
+    R, lens = c.R, (c.R != 0).sum(1)
+    assert R.shape == (c.B, c.I) and R.dtype == np.float64 and not R[:, 0].any()
+    assert c.keep.dtype == np.uint8 and c.keep.size == int(lens.sum()) and 0 < int(c.keep.sum()) < c.keep.size
+    assert c.eps.shape == (c.B, c.lat // 2) and c.eps.dtype == np.float32
+    assert (c.p, c.anneal) == (0.5, 0.2)
+    layers = VO.linear_names(c.state, "encoder") + VO.linear_names(c.state, "decoder")
+    assert len(layers) == 2 * (len(c.hidden) + 1) and all(c.state[k].dtype == np.float32 for wb in layers for k in wb)
+    d1 = (c.hidden + [c.lat])[0]
+    assert c.state["encoder.0.weight"].shape == (d1, c.I)
+    assert (d1 % 4 == 0) == name.endswith("_v4") or name == "hot_softmax"       # the kernel form the name promises
+    if name.startswith("wide_"):
+        assert 1024 < d1 <= 2048 and d1 - 1024 == (3 if name == "wide_scalar" else 4)
+    if name.startswith("nohidden_"):
+        assert c.hidden == [] and len(layers) == 2
+    if name.startswith("runs_"):
+        runs = (R != 0).sum(0)
+        assert c.B > 256 and [int(runs[i]) for i in (5, 6, 7, 36)] == [300, 256, 257, 256]
+        assert c.I - 1 == 36 and runs[36] > 0                                   # the last run of the sorted entries
+        assert sorted(np.nonzero(lens == 0)[0]) == [3, c.B - 1]
+        rows36 = np.nonzero(R[:, 36])[0]
+        assert rows36[0] < 8 and rows36[-1] > c.B - 8                           # spread over the batch
+        for item in (5, 6, 7, 36):                                              # zero coefficients inside the long runs
+            bits = c.keep[np.nonzero(R.reshape(-1))[0].searchsorted(np.nonzero(R[:, item])[0] * c.I + item)]
+            assert 0 < int(bits.sum()) < bits.size
+        vals = set(np.unique(R[R != 0]))
+        assert vals == ({1.0, 2.0, 3.0, 4.0, 5.0} if name == "runs_ratings" else {1.0})
+    if name.startswith("rows_"):
+        assert list(lens) == [256, 257, 512, 513, 3, 0]
+    if name == "hot_softmax":
+        z = VC.train_logits(name)
+        assert z.max() > 88 and (z.max(1) > 88).all() and int((lens == 0).sum()) == 1
+        bias = c.state["decoder.2.bias"]
+        assert [float(bias[i]) for i in (5, 261, 517, 9, 265, 521)] == [100, -100, 95, -100, 0, 100]
+        assert set(np.unique(bias)) == {-100.0, 0.0, 95.0, 100.0} and int((bias == 100).sum()) == 2
+    # the history arrays give R back
+    torch.manual_seed(0)
+    m = VAECF(vae_config(user_num=c.B, item_num=c.I, mlp_hidden_size=list(c.hidden), latent_dim=c.lat,
+                         history_item_id=torch.from_numpy(c.hist_id.copy()),
+                         history_item_value=torch.from_numpy(c.hist_val.copy())))
+    assert list(m.state_dict()) == list(c.state) and all(tuple(v.shape) == c.state[k].shape for k, v in m.state_dict().items())
+    np.testing.assert_array_equal(m.get_user_rating_matrix(torch.arange(c.B)).cpu().numpy(), R)
+    rp, col, val = ops.vae_history_csr(torch.from_numpy(c.hist_id.copy()), torch.from_numpy(c.hist_val.copy()), c.I)
+    assert int(rp[-1]) == c.keep.size
+    dense = np.zeros_like(R)
+    dense[np.repeat(np.arange(c.B), np.diff(rp.numpy())), col.numpy()] = val.numpy()
+    np.testing.assert_array_equal(dense, R)
+    np.testing.assert_array_equal(np.nonzero(R.reshape(-1))[0], np.repeat(np.arange(c.B), np.diff(rp.numpy())) * c.I + col.numpy())
+    # the reference's arithmetic in fp32 against the float64 oracle
+    loss, grads = VC.restated_f32(name)
+    lerr, gerr = VC.errors(loss, grads, name)
+    print(name, "fp32 restatement: loss", lerr, "worst gradient", max(gerr.values()))
+    assert np.isfinite(loss) and lerr <= 1e-5, (name, lerr)
+    for k, e in gerr.items():
+        assert e <= 1e-5, (name, k, e)

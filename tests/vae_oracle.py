@@ -23,8 +23,9 @@ def mlp(x, P, layers):
     return x
 
 
-def forward(P, R, lat, keep=None, eps=None, p=0.5, train=True):
-    """(logits, mu, logvar) in float64; R: dense [B, I] float64"""
+def forward(P, R, lat, keep=None, eps=None, p=0.5, train=True, dtype=torch.float64):
+    """(logits, mu, logvar) in `dtype` (the parameters' own); R: dense [B, I]"""
+    R = R.to(dtype)
     h = F.normalize(R)
     if train and p > 0:
         mask = torch.zeros_like(R)
@@ -36,8 +37,9 @@ def forward(P, R, lat, keep=None, eps=None, p=0.5, train=True):
     return mlp(z, P, linear_names(P, "decoder")), mu, logvar
 
 
-def loss_of(P, R, lat, keep, eps, p, anneal, train=True):
-    z, mu, logvar = forward(P, R, lat, keep, eps, p, train)
+def loss_of(P, R, lat, keep, eps, p, anneal, train=True, dtype=torch.float64):
+    R = R.to(dtype)
+    z, mu, logvar = forward(P, R, lat, keep, eps, p, train, dtype)
     kl = -0.5 * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1)) * anneal
     ce = -(F.log_softmax(z, 1) * R).sum(1).mean()
     return ce + kl
@@ -63,9 +65,10 @@ def run_steps(state, steps, lat, optimizer, lr, p, cap, total, update0=0):
     return np.array(losses), {k: v.detach() for k, v in P.items()}
 
 
-def grads_of(state, R, lat, keep, eps, p, anneal, train=True):
-    """(loss, float64 gradient of every parameter) of one step"""
-    P = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=True) for k, v in state.items()}
-    loss = loss_of(P, torch.as_tensor(np.asarray(R), dtype=torch.float64), lat, keep, eps, p, anneal, train)
+def grads_of(state, R, lat, keep, eps, p, anneal, train=True, dtype=torch.float64):
+    """(loss, gradient of every parameter) of one step in `dtype`: float64 is the oracle; with torch.float32 the same code
+    is a plain fp32 restatement of the reference's arithmetic"""
+    P = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in state.items()}
+    loss = loss_of(P, torch.tensor(np.asarray(R), dtype=dtype), lat, keep, eps, p, anneal, train, dtype)
     loss.backward()
     return float(loss.detach()), {k: v.grad.detach().numpy() for k, v in P.items()}
