@@ -103,6 +103,9 @@ SLIM_LDS_ITEMS, SLIM_MAX_TOPK = 9984, 1024
 SLIM_PATHS = {"auto": 0, "lds": 1, "global": 2}
 PSVD_MAX_C, PSVD_CONVERGED, PSVD_NOT_CONVERGED = 256, 0, 1
 EASE_BLOCK = 64
+KNN_MAX_K = 1024
+KNN_CENTER = {"none": 0, "row": 1, "col": 2, "binary": 3}
+KNN_MODES = {"cosine": 0, "asymmetric": 1, "tanimoto": 2, "dice": 3, "tversky": 4, "plain": 5}
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
@@ -249,6 +252,13 @@ SIGNATURES = {
     "daisy_ease_potri": (C.c_int, [_p, _i64, _p, _p, _p, _sz, _p]),
     "daisy_ease_weights": (C.c_int, [_p, _i64, _p, _p, _sz, _p]),
     "daisy_ease_rank": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "daisy_knn_row_means": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "daisy_knn_center": (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p]),
+    "daisy_knn_diag": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "daisy_knn_select": (C.c_int, [_p, _p, _i64, _i32, _f32, _f32, _i32, _p, _p, _p, _p]),
+    "daisy_knn_rank": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _i32, _p]),
+    "daisy_knn_fit_bytes": (_sz, [_i64, _i64, _i32]),
+    "daisy_knn_fits": (C.c_int, [_i64, _i64, _i32, _sz]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

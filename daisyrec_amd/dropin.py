@@ -66,6 +66,12 @@ def install(sampler=False, front_end=False):
         ref_ease.EASE = EASE
     except ImportError:
         pass
+    from .model.KNNCFRecommender import ItemKNNCF, UserKNNCF
+    try:                                   # the reference module imports scipy
+        ref_knn = importlib.import_module("daisy.model.KNNCFRecommender")
+        ref_knn.ItemKNNCF, ref_knn.UserKNNCF = ItemKNNCF, UserKNNCF
+    except ImportError:
+        pass
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -1692,3 +1692,149 @@ def ease_rank(csr, W, users, items=None, topk=0):
     check(lib.daisy_ease_rank(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"),
                               Cn, kk, _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
     return scores, ids
+
+
+# ---- ItemKNN / UserKNN (csrc/knn.hip; KNNCFRecommender.py) ------------------------------------------------------
+KNN_SIMILARITIES = ("cosine", "pearson", "adjusted", "asymmetric", "jaccard", "tanimoto", "dice", "tversky")
+_KNN_BINARY = {"jaccard": "tanimoto", "tanimoto": "tanimoto", "dice": "dice", "tversky": "tversky"}
+
+
+def knn_plan(similarity, normalize):
+    """(centre mode, weight mode, square-rooted norms) of a similarity name (KNNCFRecommender.py:129-151, 244-261, 313-337);
+    an unknown name raises the reference's ValueError."""
+    if similarity not in KNN_SIMILARITIES:
+        raise ValueError("value for parameter 'similarity' not recognized. Allowed values are: 'cosine', 'pearson', "
+                         "'adjusted', 'asymmetric', 'jaccard', 'tanimoto', 'dice', 'tversky'. "
+                         f"Passed value was '{similarity}'")
+    if similarity in _KNN_BINARY:
+        return "binary", _KNN_BINARY[similarity], False
+    centre = {"adjusted": "row", "pearson": "col"}.get(similarity, "none")
+    if not normalize:
+        return centre, "plain", True
+    return centre, ("asymmetric" if similarity == "asymmetric" else "cosine"), True
+
+
+def knn_row_means(csr):
+    """float32 [n_rows]: the mean of every CSR row's stored values, 0 for an empty row (daisy_knn_row_means)."""
+    rp, _, vp, R = _slim_csr_ptrs(csr)
+    mean = torch.empty(R, dtype=torch.float32, device=csr[0].device)
+    check(lib.daisy_knn_row_means(rp, vp, R, _ptr(mean, torch.float32, "mean"), _stream()))
+    return mean
+
+
+def knn_center(csr, n_cols, mode, mean=None):
+    """A CSR with the same pattern and the values centred or set to 1 (daisy_knn_center); mode: 'none' | 'row' | 'col' |
+    'binary'; mean: float32 [n_rows] ('row') or [n_cols] ('col')."""
+    rp, cp, vp, R = _slim_csr_ptrs(csr)
+    m = N.KNN_CENTER[mode]
+    if mode in ("row", "col"):
+        want = R if mode == "row" else int(n_cols)
+        if mean is None or mean.numel() != want:
+            raise ValueError(f"knn_center: mode '{mode}' needs {want} means")
+    out = torch.empty_like(csr[2])
+    if out.numel():
+        check(lib.daisy_knn_center(rp, cp, vp, R, int(n_cols), m, _ptr(mean, torch.float32, "mean"),
+                                   _ptr(out, torch.float32, "out"), _stream()))
+    return csr[0], csr[1], out
+
+
+def knn_diag(G, take_sqrt=True):
+    """float32 [n]: the diagonal of G, square-rooted unless the similarity is a binary one (daisy_knn_diag)."""
+    n = int(G.shape[0])
+    if G.dim() != 2 or G.shape[1] != n:
+        raise ValueError(f"G: expected a square matrix, got {tuple(G.shape)}")
+    ss = torch.empty(n, dtype=torch.float32, device=G.device)
+    check(lib.daisy_knn_diag(_ptr(G, torch.float32, "G"), n, int(bool(take_sqrt)), _ptr(ss, torch.float32, "ss"), _stream()))
+    return ss
+
+
+def knn_select(G, ss, mode, shrink, K, alpha=0.5):
+    """The K largest weights of every column of the symmetric G float32 [n, n] (daisy_knn_select) -> (count int32 [n],
+    rows int32 [n, K], vals float32 [n, K]) in slim_fit's fixed-pitch form, ascending row within a column; ties at the
+    boundary go to the lower row, zeros are not kept.  mode: a key of _native.KNN_MODES."""
+    n = int(G.shape[0])
+    if G.dim() != 2 or G.shape[1] != n:
+        raise ValueError(f"G: expected a square matrix, got {tuple(G.shape)}")
+    if ss.numel() != n:
+        raise ValueError(f"ss: expected {n} norms, got {ss.numel()}")
+    k = int(K)
+    count = torch.empty(n, dtype=torch.int32, device=G.device)
+    rows = torch.empty(n, max(k, 0), dtype=torch.int32, device=G.device)
+    vals = torch.empty(n, max(k, 0), dtype=torch.float32, device=G.device)
+    check(lib.daisy_knn_select(_ptr(G, torch.float32, "G"), _ptr(ss, torch.float32, "ss"), n, N.KNN_MODES[mode], float(shrink),
+                               float(alpha), k, _ptr(count, torch.int32, "count"), _ptr(rows, torch.int32, "rows"),
+                               _ptr(vals, torch.float32, "vals"), _stream()))
+    return count, rows, vals
+
+
+def knn_fit(csr_D, n, similarity, shrink, K, normalize=True, csr_Dt=None, alpha=0.5, offered_bytes=None):
+    """Similarity(D).compute_similarity() of KNNCFRecommender.py:235-377 on the device -> W by column (slim_columns'
+    triple: w_ptr int64 [n + 1], w_row int32, w_val float32).  csr_D: the CSR of D [n_rows, n] (slim_csr); csr_Dt: the CSR
+    of D^T, needed by 'pearson' alone (its column means).  Chain: centre, slim_gram, the norms, knn_select, slim_columns.
+    offered_bytes: what the fit may take (default: the device's free memory); a problem whose dense G does not fit is
+    refused before anything is allocated."""
+    centre, mode, take_sqrt = knn_plan(similarity, normalize)
+    n, k = int(n), int(K)
+    dev = csr_D[0].device
+    R = csr_D[0].numel() - 1
+    if offered_bytes is None:
+        with torch.cuda.device(dev):
+            offered_bytes = torch.cuda.mem_get_info()[0]
+    check(lib.daisy_knn_fits(R, n, k, int(offered_bytes)))
+    mean = None
+    if centre == "row":
+        mean = knn_row_means(csr_D)
+    elif centre == "col":
+        if csr_Dt is None:
+            raise ValueError("knn_fit: 'pearson' needs csr_Dt (the column means are the row means of D^T)")
+        mean = knn_row_means(csr_Dt)
+    D = knn_center(csr_D, n, centre, mean) if centre != "none" else csr_D
+    G = slim_gram(D, n, offered_bytes=offered_bytes)
+    ss = knn_diag(G, take_sqrt)
+    count, rows, vals = knn_select(G, ss, mode, shrink, k, alpha)
+    del G
+    return slim_columns(count, rows, vals, n)
+
+
+def knn_rows_of_columns(W, n):
+    """The CSR (ptr int64 [n + 1], col int32 ascending, val float32) of a square matrix given by column (slim_columns'
+    triple): UserKNN's left operand.  Torch ops, once per fit."""
+    w_ptr, w_row, w_val = W
+    nnz = int(w_ptr[-1].item())
+    dev = w_ptr.device
+    colid = torch.repeat_interleave(torch.arange(n, device=dev, dtype=torch.int64), w_ptr[1:] - w_ptr[:-1])
+    r = w_row[:nnz].to(torch.int64)
+    order = torch.argsort(r * max(n, 1) + colid)
+    ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.cumsum(torch.bincount(r, minlength=n), 0) if nnz else 0
+    col, val = colid[order].to(torch.int32).contiguous(), w_val[:nnz][order].contiguous()
+    if nnz == 0:
+        col, val = col.new_zeros(1), val.new_zeros(1)
+    return ptr, col, val
+
+
+def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
+    """float64 scores [B, C] = L[users] R at the candidates items [B, C] (None: every column) and, for topk > 0, the ids
+    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_knn_rank).  L: a
+    CSR triple [*, inner]; R: a by-column triple [inner, n_cols].  -> (scores, ids or None)"""
+    lp, lc, lv, n_rows = _slim_csr_ptrs(L)
+    rp, rc, rv, nc = _slim_csr_ptrs(R)
+    if nc != int(n_cols):
+        raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
+    users = users.to(torch.int64).contiguous()
+    B = users.numel()
+    if items is not None:
+        items = items.to(torch.int64).contiguous()
+        if items.dim() != 2 or items.shape[0] != B:
+            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
+        Cn = int(items.shape[1])
+    else:
+        Cn = int(n_cols)
+    dev = L[0].device
+    scores = torch.empty(B, Cn, dtype=torch.float64, device=dev)
+    kk = min(int(topk), Cn)
+    ids = torch.empty(B, kk, dtype=torch.int64, device=dev) if kk > 0 else None
+    check(lib.daisy_knn_rank(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols), _ptr(users, torch.int64, "users"), B,
+                             _ptr(items, torch.int64, "items"), Cn, kk, _ptr(scores, torch.float64, "scores"),
+                             _ptr(ids, torch.int64, "ids"), N.SLIM_PATHS[path], _stream()))
+    return scores, ids

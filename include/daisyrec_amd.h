@@ -1047,6 +1047,64 @@ int daisy_ease_rank(const int64_t *row_ptr, const int32_t *col, const float *val
                     int64_t item_num, const int64_t *users, int64_t B, const int64_t *items, int64_t C, int32_t topk,
                     double *scores, int64_t *out_ids, daisy_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * ItemKNN / UserKNN (daisy/model/KNNCFRecommender.py, Similarity / ItemKNNCF / UserKNNCF): the similarity of the columns
+ * of a data matrix D [n_rows, n] (X for ItemKNN, X^T for UserKNN) from G = D^T D (daisy_slim_gram), the K largest
+ * weights of every column, and the fp64 scores (csrc/knn.hip).  D is a CSR of daisy_slim_gram's layout.
+ * Reproducible run to run: no floating-point atomics, every floating-point sum in a fixed order.
+ * ---------------------------------------------------------------------- */
+#define DAISY_KNN_MAX_K 1024
+/* what daisy_knn_center does to the stored values of D */
+enum { DAISY_KNN_CENTER_NONE = 0, DAISY_KNN_CENTER_ROW = 1, DAISY_KNN_CENTER_COL = 2, DAISY_KNN_CENTER_BINARY = 3 };
+/* the weight of daisy_knn_select (KNNCFRecommender.py:313-337); PLAIN: w / shrink when shrink != 0, else w */
+enum { DAISY_KNN_COSINE = 0, DAISY_KNN_ASYMMETRIC = 1, DAISY_KNN_TANIMOTO = 2, DAISY_KNN_DICE = 3, DAISY_KNN_TVERSKY = 4,
+       DAISY_KNN_PLAIN = 5 };
+/* KNNCFRecommender.py:172-178: mean[r] = the fp32 sum of row r's stored values (a wave per row: lane l adds the entries
+ * l, l + 64, ... in stored order, the lanes meet in a fixed tree) divided by their count; 0 for an empty row. */
+int daisy_knn_row_means(const int64_t *row_ptr, const float *val, int64_t n_rows, float *mean, daisy_stream_t stream);
+/* KNNCFRecommender.py:165-233: out[e] = val[e] - mean[row of e] (CENTER_ROW, mean [n_rows]: 'adjusted'), val[e] -
+ * mean[col[e]] (CENTER_COL, mean [n_cols]: 'pearson'; the column means are the row means of the other orientation's CSR),
+ * 1 (CENTER_BINARY: jaccard, tanimoto, dice, tversky) or val[e] (CENTER_NONE).  A value that becomes exactly 0 stays
+ * stored.  out may be val. */
+int daisy_knn_center(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows, int64_t n_cols,
+                     int32_t mode, const float *mean, float *out, daisy_stream_t stream);
+/* KNNCFRecommender.py:257-261: ss[i] = G[i, i], its correctly rounded square root when take_sqrt != 0. */
+int daisy_knn_diag(const float *G, int64_t n, int32_t take_sqrt, float *ss, daisy_stream_t stream);
+/* KNNCFRecommender.py:302-356 for every column j of the symmetric G fp32 [n, n]: w[i] = G[j, i], w[j] = 0, then in fp32,
+ * every operation rounded on its own (no fused multiply-add):
+ *   COSINE      w * (1 / (ss[j] * ss[i] + shrink + 1e-6))
+ *   ASYMMETRIC  w * (1 / (ss[j]^(2 alpha) * ss[i]^(2 (1 - alpha)) + shrink + 1e-6)); alpha == 0.5 takes COSINE's path
+ *   TANIMOTO    w * (1 / (ss[j] + ss[i] - w + shrink + 1e-6))
+ *   DICE        w * (1 / (ss[j] + ss[i] + shrink + 1e-6))
+ *   TVERSKY     w * (1 / (w + (ss[j] - w) + (ss[i] - w) + shrink + 1e-6))
+ *   PLAIN       w / shrink when shrink != 0, else w
+ * Of the min(K, n) largest weights of the column, as signed values with -0.0 == +0.0, the non-zero ones are kept: ties at
+ * the boundary go to the LOWER row (the reference leaves them to argpartition).  Outputs in daisy_slim_cd's fixed-pitch
+ * form: count int32 [n]; rows int32 / vals float32 [n, K], ascending row within a column, unused slots (-1, 0).
+ * One workgroup per column at a time: the K-th largest weight by a radix select over an order-preserving 32-bit key
+ * (four histogram passes of 8 bits, integer atomics in LDS), one ordered pass that assigns the slots by a workgroup
+ * prefix scan; the weights are recomputed on every pass, so n is not bounded by the LDS.  1 <= K <= DAISY_KNN_MAX_K (K >=
+ * n is allowed), shrink finite and >= 0, 0 <= alpha <= 1. */
+int daisy_knn_select(const float *G, const float *ss, int64_t n, int32_t mode, float shrink, float alpha, int32_t K,
+                     int32_t *count, int32_t *rows, float *vals, daisy_stream_t stream);
+/* KNNCFRecommender.py:432 / :510 and predict, rank, full_rank: scores[B, C] (fp64) = sum over k ascending of
+ * L[users[b], k] * R[k, item], L a CSR [n_rows, inner] with fp32 values, R [inner, n_cols] by column (r_ptr int64
+ * [n_cols + 1], r_row int32 ascending within a column, r_val fp32), at the candidates items[B][C] (items == NULL: every
+ * column, C = n_cols); then, unless out_ids == NULL, out_ids [B, topk] = the candidates' ids (positions when items ==
+ * NULL) of the largest scores, compared as fp64, ties to the lower position.  ItemKNN: L = X, R = W by column; UserKNN:
+ * L = W by row, R = X by column.  One workgroup per row: L's row is scattered into LDS (path LDS; AUTO up to inner =
+ * 32768) or looked up by binary search (path GLOBAL; DAISY_SLIM_PATH_*).  An id out of range scores 0. */
+int daisy_knn_rank(const int64_t *l_ptr, const int32_t *l_col, const float *l_val, int64_t n_rows, int64_t inner,
+                   const int64_t *r_ptr, const int32_t *r_row, const float *r_val, int64_t n_cols, const int64_t *users,
+                   int64_t B, const int64_t *items, int64_t C, int32_t topk, double *scores, int64_t *out_ids, int32_t path,
+                   daisy_stream_t stream);
+/* bytes a fit of D [n_rows, n] holds at its peak: G (n^2 fp32), the workspace of daisy_slim_gram, and the outputs of
+ * daisy_knn_select with the norms.  The dense G bounds n (UserKNN: n = user_num).  0 on bad arguments. */
+size_t daisy_knn_fit_bytes(int64_t n_rows, int64_t n, int32_t K);
+/* DAISY_OK when daisy_knn_fit_bytes <= offered_bytes, else DAISY_ERR_ARG with the sizes in daisy_last_error(); makes no
+ * HIP call: callers refuse a fit before anything is allocated. */
+int daisy_knn_fits(int64_t n_rows, int64_t n, int32_t K, size_t offered_bytes);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
