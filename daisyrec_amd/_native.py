@@ -106,6 +106,11 @@ EASE_BLOCK = 64
 KNN_MAX_K = 1024
 KNN_CENTER = {"none": 0, "row": 1, "col": 2, "binary": 3}
 KNN_MODES = {"cosine": 0, "asymmetric": 1, "tanimoto": 2, "dice": 3, "tversky": 4, "plain": 5}
+# daisy_ranking_kpis: bit (1 << id) of the metrics mask; the first KPI_PER_USER have a value per list
+KPI_IDS = {"precision": 0, "recall": 1, "hit": 2, "mrr": 3, "map": 4, "ndcg": 5, "f1": 6, "auc": 7, "popularity": 8,
+           "diversity": 9, "coverage": 10}
+KPI_PER_USER = 10
+METRICS_MAX_K, METRICS_MAX_CUTOFFS, METRICS_MAX_CATS = 256, 12, 256
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
 SIGNATURES = {
@@ -259,6 +264,11 @@ SIGNATURES = {
     "daisy_knn_rank": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _i32, _p]),
     "daisy_knn_fit_bytes": (_sz, [_i64, _i64, _i32]),
     "daisy_knn_fits": (C.c_int, [_i64, _i64, _i32, _sz]),
+    "daisy_pop_fit": (C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
+    "daisy_pop_rank": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
+    "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),
+    "daisy_ranking_kpis": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _i64, _p, _i32,
+                                     _i32, _p, C.c_uint32, _p, _p, _p, _p, _sz, _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

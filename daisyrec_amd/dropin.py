@@ -11,8 +11,16 @@ from __future__ import annotations
 import importlib
 
 
-def install(sampler=False, front_end=False):
+# what install(metrics=True) rebinds in daisy.utils.metrics
+METRICS_NAMES = ("metrics_name_config", "calc_ranking_results", "Metric", "Coverage", "Popularity", "Diversity", "Precision",
+                 "Recall", "MRR", "MAP", "NDCG", "HR", "AUC", "F1")
+
+
+def install(sampler=False, front_end=False, metrics=False):
     """Patch `daisy.model.MFRecommender.MF` (and the other mirrored recommenders) in place.
+    metrics: also `daisy.utils.metrics` - `calc_ranking_results`, `Metric`, `metrics_name_config` and the eleven KPI
+    functions (one device pass for all cutoffs instead of a Python loop per user, KPI and cutoff).  Like front_end: call
+    before the driver module is imported (test.py:18 binds `calc_ranking_results`, tune.py:23 the KPI functions at import).
     sampler: also the negative sampler (device generator: same distribution, different stream than MT19937).
     front_end: also `daisy.utils.utils.get_ur / get_ir` (same dicts, built from one sort instead of a Python row
     loop) and `build_candidates_set` (device generator) - what makes the drivers usable beyond ml-100k sizes
@@ -72,6 +80,15 @@ def install(sampler=False, front_end=False):
         ref_knn.ItemKNNCF, ref_knn.UserKNNCF = ItemKNNCF, UserKNNCF
     except ImportError:
         pass
+    from .model.PopRecommender import MostPop
+    ref_pop = importlib.import_module("daisy.model.PopRecommender")
+    ref_pop.MostPop = MostPop
+    if metrics:
+        from .utils import metrics as M
+
+        ref_m = importlib.import_module("daisy.utils.metrics")
+        for name in METRICS_NAMES:
+            setattr(ref_m, name, getattr(M, name))
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

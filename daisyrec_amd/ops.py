@@ -1838,3 +1838,85 @@ def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
                              _ptr(items, torch.int64, "items"), Cn, kk, _ptr(scores, torch.float64, "scores"),
                              _ptr(ids, torch.int64, "ids"), N.SLIM_PATHS[path], _stream()))
     return scores, ids
+
+
+# ---- MostPop and the ranking KPIs (csrc/pop.hip, csrc/metrics.hip) ----------------------------------------
+def _ids_ptr(t, name):
+    """(pointer, is_i64) of a contiguous int32 / int64 device tensor of ids"""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.int32:
+        return _ptr(t, torch.int32, name), 0
+    return _ptr(t, torch.int64, name), 1
+
+
+def pop_fit(items, item_num):
+    """PopRecommender.py:30-33: (cnt int64 [item_num], score float64 [item_num] = cnt / (1 + cnt)) of the item column
+    (int32 / int64, device)."""
+    items = items.contiguous()
+    ip, is64 = _ids_ptr(items, "items")
+    cnt = torch.empty(int(item_num), dtype=torch.int64, device=items.device)
+    score = torch.empty(int(item_num), dtype=torch.float64, device=items.device)
+    check(lib.daisy_pop_fit(ip if items.numel() else None, is64, items.numel(), int(item_num), _ptr(cnt, torch.int64, "cnt"),
+                            _ptr(score, torch.float64, "score"), _stream()))
+    return cnt, score
+
+
+def pop_rank(score, items=None, topk=1):
+    """ids int64 [B, min(topk, C)] of the largest score[items[b]] (items int64 [B, C]), compared as float64, ties to the
+    lower candidate position; items None: the full rank over all items, [1, topk] (daisy_pop_rank)."""
+    I = score.numel()
+    if items is None:
+        B, Cn, gathered = 1, I, None
+    else:
+        items = items.to(torch.int64).contiguous()
+        if items.dim() != 2:
+            raise ValueError(f"items: expected [B, C], got {tuple(items.shape)}")
+        B, Cn = int(items.shape[0]), int(items.shape[1])
+        gathered = torch.empty(B, Cn, dtype=torch.float64, device=score.device)
+    kk = min(int(topk), Cn)
+    ids = torch.empty(B, max(kk, 0), dtype=torch.int64, device=score.device)
+    check(lib.daisy_pop_rank(_ptr(score, torch.float64, "score"), I, _ptr(items, torch.int64, "items"), B, Cn, kk,
+                             _ptr(gathered, torch.float64, "gathered"), _ptr(ids, torch.int64, "ids"), _stream()))
+    return ids
+
+
+def kpi_mask(metrics):
+    mask = 0
+    for name in metrics:
+        if name not in N.KPI_IDS:
+            raise ValueError(f"Invalid metric name {name}")          # metrics.py:92
+        mask |= 1 << N.KPI_IDS[name]
+    return mask
+
+
+def ranking_kpis(pred, indptr, gt_items, users, cutoffs, metrics, item_num, disc=None, item_pop=None, cat_bits=None,
+                 n_cats=0, sqrt_tab=None, per_user=False):
+    """daisy_ranking_kpis: every requested KPI at every cutoff in one pass over pred (int32 / int64 [n, K], device).
+    -> (names, per_user, means, cover): names = the requested per-list KPIs in slot order, per_user float64
+    [len(names), nc, n] or None, means float64 [len(names), nc], cover int64 [nc] or None (the distinct ids of
+    pred[:, :k])."""
+    pred = pred.contiguous()
+    if pred.dim() != 2:
+        raise ValueError(f"pred: expected [n, K], got {tuple(pred.shape)}")
+    n, K = int(pred.shape[0]), int(pred.shape[1])
+    pp, is64 = _ids_ptr(pred, "pred")
+    mask = kpi_mask(metrics)
+    names = [m for m in sorted(N.KPI_IDS, key=N.KPI_IDS.get) if N.KPI_IDS[m] < N.KPI_PER_USER and mask >> N.KPI_IDS[m] & 1]
+    cuts = (C.c_int32 * max(len(cutoffs), 1))(*[int(k) for k in cutoffs])
+    nc = len(cutoffs)
+    dev = pred.device
+    users = users.to(torch.int64).contiguous()
+    if users.numel() != n:
+        raise ValueError(f"users: {users.numel()} owners for {n} lists")
+    out_user = torch.empty(len(names), nc, n, dtype=torch.float64, device=dev) if (per_user and names) else None
+    means = torch.empty(len(names), nc, dtype=torch.float64, device=dev)
+    cover = torch.empty(nc, dtype=torch.int64, device=dev) if "coverage" in metrics else None
+    ws = _ws(lib.daisy_ranking_kpis_workspace_bytes(n, nc, int(item_num), mask), dev)
+    words = 0 if cat_bits is None else int(cat_bits.shape[1])
+    cat_ptr = None if cat_bits is None else _ptr(cat_bits.view(torch.int64), torch.int64, "cat_bits")
+    check(lib.daisy_ranking_kpis(pp, is64, n, K, _ptr(indptr, torch.int64, "indptr"), _ptr(gt_items, torch.int32, "gt_items"),
+                                 indptr.numel() - 1, _ptr(users, torch.int64, "users"), cuts, nc,
+                                 _ptr(disc, torch.float64, "disc"), _ptr(item_pop, torch.float64, "item_pop"), int(item_num),
+                                 cat_ptr, words, int(n_cats), _ptr(sqrt_tab, torch.float64, "sqrt_tab"), mask,
+                                 _ptr(out_user, torch.float64, "per_user"), _ptr(means, torch.float64, "means"),
+                                 _ptr(cover, torch.int64, "cover"), _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return names, out_user, means, cover

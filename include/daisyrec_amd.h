@@ -1105,6 +1105,72 @@ size_t daisy_knn_fit_bytes(int64_t n_rows, int64_t n, int32_t K);
  * HIP call: callers refuse a fit before anything is allocated. */
 int daisy_knn_fits(int64_t n_rows, int64_t n, int32_t K, size_t offered_bytes);
 
+/* ------------------------------------------------------------------------
+ * MostPop (daisy/model/PopRecommender.py) and the ranking KPIs (daisy/utils/metrics.py): csrc/pop.hip, csrc/metrics.hip;
+ * DESIGN.md §20.
+ * ---------------------------------------------------------------------- */
+/* PopRecommender.py:30-33 (fit): cnt int64 [item_num] = the occurrences of every id in items [nnz] (int32, or int64 when
+ * items_is_i64 != 0; an id outside [0, item_num) is skipped), by integer atomics; score fp64 [item_num] = cnt / (1 + cnt),
+ * the reference's one division on float64 counts, hence its bits. */
+int daisy_pop_fit(const void *items, int32_t items_is_i64, int64_t nnz, int64_t item_num, int64_t *cnt, double *score,
+                  daisy_stream_t stream);
+/* PopRecommender.py:35-54 (predict, rank, full_rank): gathered [B, C] (fp64) = score[items[b][c]] (0 for an id out of
+ * range), out_ids [B, topk] = the candidates' ids of the largest scores, compared as fp64, ties to the lower candidate
+ * position (the reference's argsort leaves them open).  items == NULL: the full rank - one row (B <= 1), C = item_num,
+ * gathered unused (may be NULL), out_ids = positions.  1 <= topk <= C. */
+int daisy_pop_rank(const double *score, int64_t item_num, const int64_t *items, int64_t B, int64_t C, int32_t topk,
+                   double *gathered, int64_t *out_ids, daisy_stream_t stream);
+
+/* The KPIs of daisy_ranking_kpis: bit (1 << id) of its `metrics` mask.  The first DAISY_KPI_PER_USER have a value per
+ * list; the requested ones take the slots 0, 1, ... of the outputs in this order.  Coverage has only its counts. */
+enum {
+    DAISY_KPI_PRECISION = 0,  /* metrics.py:148-158 */
+    DAISY_KPI_RECALL = 1,     /* metrics.py:160-170 */
+    DAISY_KPI_HIT = 2,        /* metrics.py:229-239 */
+    DAISY_KPI_MRR = 3,        /* metrics.py:172-186 */
+    DAISY_KPI_MAP = 4,        /* metrics.py:188-202 */
+    DAISY_KPI_NDCG = 5,       /* metrics.py:204-227 */
+    DAISY_KPI_F1 = 6,         /* metrics.py:263-278 */
+    DAISY_KPI_AUC = 7,        /* metrics.py:241-261 */
+    DAISY_KPI_POPULARITY = 8, /* metrics.py:104-122 */
+    DAISY_KPI_DIVERSITY = 9,  /* metrics.py:124-146 */
+    DAISY_KPI_PER_USER = 10,
+    DAISY_KPI_COVERAGE = 10,  /* metrics.py:98-102 */
+    DAISY_KPI_COUNT = 11
+};
+#define DAISY_METRICS_MAX_K 256
+#define DAISY_METRICS_MAX_CUTOFFS 12
+#define DAISY_METRICS_MAX_CATS 256
+#define DAISY_METRICS_MAX_CAT_WORDS 4
+/* bytes of daisy_ranking_kpis' workspace (the workgroups' partial sums; the coverage bitmaps); 0 on bad arguments */
+size_t daisy_ranking_kpis_workspace_bytes(int64_t n, int32_t nc, int64_t item_num, uint32_t metrics);
+/* calc_ranking_results / Metric.run (metrics.py:18-96) for ALL cutoffs and ALL requested KPIs in one pass over pred.
+ *   pred [n, K] item ids, row-major, best first (int32, or int64 when pred_is_i64 != 0); an id outside [0, item_num) is
+ *   never a hit.  indptr / gt_items: the truths as daisy_build_user_csr's CSR over user_num users.  users int64 [n]: the
+ *   owner of every list (test_u; any order, repeats allowed; a user outside [0, user_num) has no truths).
+ *   cutoffs_host int32 [nc]: HOST memory (they travel as kernel arguments), >= 1, strictly ascending, <= K <=
+ *   DAISY_METRICS_MAX_K, nc <= DAISY_METRICS_MAX_CUTOFFS.  disc fp64 [K] = 1 / log2(p + 2), built on the host (needed for
+ *   ndcg).  item_pop fp64 [item_num] (needed for popularity).  cat_bits uint64 [item_num, cat_words]: bit c of an item's
+ *   row = it has category c, n_cats <= DAISY_METRICS_MAX_CATS, cat_words = ceil(n_cats / 64); sqrt_tab fp64 [n_cats + 1] =
+ *   sqrt(0 .. n_cats) (both needed for diversity).
+ * With r the hit mask of the first k positions (binary search in the user's row; duplicates count per position, as
+ * np.in1d counts them), hits = popcount(r), gt = the row's length:
+ *   precision hits / k; recall hits / gt; hit 1 or 0; mrr 1 / (first hit + 1) or 0; map the mean over the hit positions p
+ *   of popcount(r[:p + 1]) / (p + 1) or 0; ndcg sum_{p hit} disc[p] / sum_{p < hits} disc[p] or 0; f1 2 pre rec / (pre +
+ *   rec); auc (the pairs hit-before-miss) / (hits (k - hits)) - 0 / 0 is NaN for f1 and auc, as in the reference;
+ *   popularity sum of item_pop over the DISTINCT hit items / gt or 0; diversity the mean over the pairs i < j < k of
+ *   sqrt_tab[popcount(cat[pred_i] xor cat[pred_j])], NaN for k = 1.
+ * Outputs: per_user fp64 [slots, nc, n] (may be NULL), means fp64 [slots, nc] (the sum of a workgroup's 256 lists, then
+ * of the workgroups, both in a fixed order, divided by n: a NaN value makes its mean NaN), cover_counts int64 [nc] = the
+ * distinct in-range ids of pred[:, :k] (integer atomic OR on a bitmap per cutoff, then popcounts).  No floating-point
+ * atomics: two calls give the same bits.  One wave per list; lists longer than 64 run in chunks of 64. */
+int daisy_ranking_kpis(const void *pred, int32_t pred_is_i64, int64_t n, int32_t K, const int64_t *indptr,
+                       const int32_t *gt_items, int64_t user_num, const int64_t *users, const int32_t *cutoffs_host,
+                       int32_t nc, const double *disc, const double *item_pop, int64_t item_num, const uint64_t *cat_bits,
+                       int32_t cat_words, int32_t n_cats, const double *sqrt_tab, uint32_t metrics, double *per_user,
+                       double *means, int64_t *cover_counts, void *workspace, size_t workspace_bytes,
+                       daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
