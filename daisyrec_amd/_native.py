@@ -269,6 +269,10 @@ SIGNATURES = {
     "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),
     "daisy_ranking_kpis": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _i64, _p, _i32,
                                      _i32, _p, C.c_uint32, _p, _p, _p, _p, _sz, _p]),
+    "daisy_prep_encode": (C.c_int, [_p, _i64, _p, _p, C.POINTER(_i64), _p]),
+    "daisy_prep_process": (C.c_int, [_p, _p, _p, _p, _i64, _i32, C.c_double, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p,
+                                     C.POINTER(_i64), _p]),
+    "daisy_split_ids": (C.c_int, [_i32, _p, _p, _i64, _i64, C.c_double, C.c_double, _u64, _u64, _p, _p, C.POINTER(_i64), _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

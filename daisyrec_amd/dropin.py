@@ -16,8 +16,16 @@ METRICS_NAMES = ("metrics_name_config", "calc_ranking_results", "Metric", "Cover
                  "Recall", "MRR", "MAP", "NDCG", "HR", "AUC", "F1")
 
 
-def install(sampler=False, front_end=False, metrics=False):
+# what install(prep=True) rebinds in daisy.utils.splitter (and Preprocessor in daisy.utils.loader)
+SPLITTER_NAMES = ("TestSplitter", "ValidationSplitter", "split_test", "split_validation")
+
+
+def install(sampler=False, front_end=False, metrics=False, prep=False):
     """Patch `daisy.model.MFRecommender.MF` (and the other mirrored recommenders) in place.
+    prep: also `daisy.utils.loader.Preprocessor` and `daisy.utils.splitter`'s `TestSplitter`, `ValidationSplitter`,
+    `split_test`, `split_validation` (dedup, k-core, encoding, time sort and every split on the device instead of Python
+    loops over rows and users; DESIGN.md section 21 lists the deviations).  Like front_end: call before the driver module
+    is imported (test.py:5-6 binds the classes at import).  Without it both modules are left untouched.
     metrics: also `daisy.utils.metrics` - `calc_ranking_results`, `Metric`, `metrics_name_config` and the eleven KPI
     functions (one device pass for all cutoffs instead of a Python loop per user, KPI and cutoff).  Like front_end: call
     before the driver module is imported (test.py:18 binds `calc_ranking_results`, tune.py:23 the KPI functions at import).
@@ -89,6 +97,14 @@ def install(sampler=False, front_end=False, metrics=False):
         ref_m = importlib.import_module("daisy.utils.metrics")
         for name in METRICS_NAMES:
             setattr(ref_m, name, getattr(M, name))
+    if prep:
+        from .utils import loader as L, splitter as S
+
+        ref_l = importlib.import_module("daisy.utils.loader")
+        ref_l.Preprocessor = L.Preprocessor
+        ref_sp = importlib.import_module("daisy.utils.splitter")
+        for name in SPLITTER_NAMES:
+            setattr(ref_sp, name, getattr(S, name))
     if sampler:
         from .utils.sampler import BasicNegtiveSampler
 

@@ -1920,3 +1920,62 @@ def ranking_kpis(pred, indptr, gt_items, users, cutoffs, metrics, item_num, disc
                                  _ptr(out_user, torch.float64, "per_user"), _ptr(means, torch.float64, "means"),
                                  _ptr(cover, torch.int64, "cover"), _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
     return names, out_user, means, cover
+
+
+# ---- Preprocessor and splitters (csrc/prep.hip, csrc/split.hip) -------------------------------------------
+PREP_MODES = {"origin": 0, "filter": 1, "core": 2}
+PREP_LEVELS = {"u": 1, "i": 2, "ui": 3}
+SPLIT_METHODS = {"tloo": 0, "utfo": 1, "ufo": 2, "rloo": 3, "rsbr": 4}
+
+
+def prep_encode(ids):
+    """(codes int32 [n], tokens int64 [distinct]) of an int64 device column: the rank of every id among the column's
+    distinct values, and those values ascending (daisy_prep_encode)."""
+    ids = ids.contiguous()
+    n = ids.numel()
+    codes = torch.empty(n, dtype=torch.int32, device=ids.device)
+    tokens = torch.empty(n, dtype=torch.int64, device=ids.device)
+    distinct = C.c_int64(0)
+    check(lib.daisy_prep_encode(_ptr(ids, torch.int64, "ids"), n, _ptr(codes, torch.int32, "codes"),
+                                _ptr(tokens, torch.int64, "tokens"), C.byref(distinct), _stream()))
+    return codes, tokens[:distinct.value]
+
+
+def prep_process(users, items, rating, timestamp, threshold=None, mode="origin", level="ui", N=1, want_pop=False):
+    """daisy_prep_process on int64 device columns (rating float64, None without a threshold).  -> dict: rows int64 [m]
+    (positions in the input, final order), user / item int32 [m], uid_token / iid_token int64, item_pop float64
+    [item_num] or None, user_num, item_num, rounds (peel rounds that removed rows)."""
+    users, items, timestamp = users.contiguous(), items.contiguous(), timestamp.contiguous()
+    n, dev = users.numel(), users.device
+    if items.numel() != n or timestamp.numel() != n or (rating is not None and rating.numel() != n):
+        raise ValueError(f"prep_process: columns of different lengths ({n} users)")
+    rows = torch.empty(n, dtype=torch.int64, device=dev)
+    uc, ic = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    ut, it = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2))
+    pop = torch.empty(n, dtype=torch.float64, device=dev) if want_pop else None
+    stats = (C.c_int64 * 4)()
+    check(lib.daisy_prep_process(_ptr(users, torch.int64, "users"), _ptr(items, torch.int64, "items"),
+                                 _ptr(None if rating is None else rating.contiguous(), torch.float64, "rating"),
+                                 _ptr(timestamp, torch.int64, "timestamp"), n, int(threshold is not None),
+                                 float(threshold) if threshold is not None else 0.0, PREP_MODES[mode], PREP_LEVELS[level],
+                                 int(N), int(bool(want_pop)), _ptr(rows, torch.int64, "rows"), _ptr(uc, torch.int32, "user"),
+                                 _ptr(ic, torch.int32, "item"), _ptr(ut, torch.int64, "uid_token"),
+                                 _ptr(it, torch.int64, "iid_token"), _ptr(pop, torch.float64, "item_pop"), stats, _stream()))
+    m, user_num, item_num, rounds = (int(x) for x in stats)
+    return {"rows": rows[:m], "user": uc[:m], "item": ic[:m], "uid_token": ut[:user_num], "iid_token": it[:item_num],
+            "item_pop": pop[:item_num] if want_pop else None, "user_num": user_num, "item_num": item_num, "rounds": rounds}
+
+
+def split_ids(method, n, user_code=None, user_num=0, timestamp=None, size=0.5, seed=0, fold=0, device=None):
+    """daisy_split_ids: (train int64, test int64) positions of a frame of n rows.  user_code int32 [n] dense codes
+    (prep_encode), timestamp int64 [n] for tloo.  1 - size is formed here, on the host, as the reference forms it."""
+    dev = user_code.device if user_code is not None else torch.device(device or "cuda")
+    train = torch.empty(n, dtype=torch.int64, device=dev)
+    test = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = (C.c_int64 * 2)()
+    size = float(size)
+    check(lib.daisy_split_ids(SPLIT_METHODS[method], _ptr(user_code, torch.int32, "user_code"),
+                              _ptr(timestamp, torch.int64, "timestamp"), int(n), int(user_num), size, 1 - size,
+                              int(seed) & (2 ** 64 - 1), int(fold), _ptr(train, torch.int64, "train"),
+                              _ptr(test, torch.int64, "test"), counts, _stream()))
+    return train[:counts[0]], test[:counts[1]]

@@ -1171,6 +1171,45 @@ int daisy_ranking_kpis(const void *pred, int32_t pred_is_i64, int64_t n, int32_t
                        double *means, int64_t *cover_counts, void *workspace, size_t workspace_bytes,
                        daisy_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Preprocessor.process (daisy/utils/loader.py:176-189) and split_test / split_validation (daisy/utils/splitter.py):
+ * csrc/prep.hip, csrc/split.hip; DESIGN.md §21.  Integer work throughout: no floating-point atomics, two calls give the
+ * same bytes.  The entries allocate their own scratch, read a few totals back and return with the stream drained.
+ * ---------------------------------------------------------------------- */
+/* codes int32 [n] = the rank of ids[e] (any int64) among the column's distinct values; tokens int64 [n]: the distinct
+ * values ascending in its first *n_distinct_host (HOST) places.  Sort, run heads, scan, scatter.  1 <= n < 2^31. */
+int daisy_prep_encode(const int64_t *ids, int64_t n, int32_t *codes, int64_t *tokens, int64_t *n_distinct_host,
+                      daisy_stream_t stream);
+enum { DAISY_PREP_ORIGIN = 0, DAISY_PREP_FILTER = 1, DAISY_PREP_CORE = 2 };      /* prepro 'origin', 'Nfilter', 'Ncore' */
+/* The whole of process() on the raw columns users / items / timestamp (int64 [n]) and rating (fp64 [n]; may be NULL
+ * without a threshold):
+ *   drop_duplicates([user, item], keep='last') - the largest row number of every pair stays;
+ *   rating >= threshold when use_threshold != 0 (a NaN is dropped);
+ *   mode FILTER, or CORE at level 1 (u) / 2 (i): one pass against the counts of that frame; CORE at level 3 (ui):
+ *   round-synchronous peeling - every live row whose user or item has < N live rows leaves, the counts follow, until a
+ *   round removes nothing (one word read by the host per round);
+ *   the category codes of the survivors and their tokens; the stable sort by timestamp (ties stay in row order);
+ *   item_pop fp64 [item_num] = count / user_num when want_pop != 0.
+ * Outputs (device, room for n each): rows int64 = positions in the input in final order, user_code / item_code int32,
+ * uid_token / iid_token int64 ascending, item_pop.  stats_host int64 [4] (HOST) = rows kept, user_num, item_num, peel
+ * rounds that removed rows.  1 <= n < 2^31, N >= 1. */
+int daisy_prep_process(const int64_t *users, const int64_t *items, const double *rating, const int64_t *timestamp, int64_t n,
+                       int32_t use_threshold, double threshold, int32_t mode, int32_t level, int32_t N, int32_t want_pop,
+                       int64_t *rows, int32_t *user_code, int32_t *item_code, int64_t *uid_token, int64_t *iid_token,
+                       double *item_pop, int64_t *stats_host, daisy_stream_t stream);
+enum { DAISY_SPLIT_TLOO = 0, DAISY_SPLIT_UTFO = 1, DAISY_SPLIT_UFO = 2, DAISY_SPLIT_RLOO = 3, DAISY_SPLIT_RSBR = 4 };
+/* splitter.py:50-86 over dense user codes (int32 [n], < user_num; unused by RSBR):
+ *   TLOO  per user the row of the largest timestamp (int64 [n]), ties to the earliest row; test in ascending row order;
+ *   UTFO  per user the rows after its first ceil(len * one_minus_size) in row order (one_minus_size = 1 - size from the
+ *         caller, as the reference forms it);
+ *   UFO / RLOO / RSBR  every row gets the Philox key of (seed, fold, row); the first rint(len * size) rows of every user
+ *         in key order (UFO), the first one (RLOO), the first (int64)(n * size) of all rows (RSBR).
+ * test int64 [n]: users ascending, within a user by row (UTFO) or key (random methods); train int64 [n]: the complement,
+ * ascending.  counts_host int64 [2] (HOST) = the lengths of train and test.  1 <= n < 2^31, 0 < size < 1. */
+int daisy_split_ids(int32_t method, const int32_t *user_code, const int64_t *timestamp, int64_t n, int64_t user_num, double size,
+                    double one_minus_size, uint64_t seed, uint64_t fold, int64_t *train, int64_t *test, int64_t *counts_host,
+                    daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
