@@ -63,7 +63,9 @@ __global__ void k_lg_read(const uint32_t *__restrict__ ekey, const uint2 *__rest
 
 // reproducible product: the lane group that sees the first entry of a row owns it and sums the row's
 // entries in stored order (fixed, so bitwise reproducible; serial over long rows - the throughput
-// path is segsum_rows)
+// path is segsum_rows).  The running sum is a double: one fp32 accumulator over a row of g entries is off by up to
+// g / 2 ulps - measured: 6e-5 of the row at g = 8192 (tests/test_gpu_segment_layouts.py), three times the tolerance
+// the chunked path meets - and the loop waits for its dependent loads, not for the adds.
 __global__ __launch_bounds__(kBlock) void k_lg_spmm_owner(const uint32_t *__restrict__ ekey,
                                                           const uint2 *__restrict__ esu,
                                                           const float2 *__restrict__ coef, int64_t n,
@@ -76,10 +78,10 @@ __global__ __launch_bounds__(kBlock) void k_lg_spmm_owner(const uint32_t *__rest
         if (pos > 0 && ekey[pos - 1] == key) continue;          // not the head of its row
         const int64_t row = key >> 1;
         for (int c = lane; c < d; c += 16) {
-            float acc = 0.f;
+            double acc = 0.0;
             for (int64_t q = pos; q < n && ekey[q] == key; ++q)
-                acc = fmaf(coef[q].x, X[(int64_t)esu[q].y * d + c], acc);
-            Y[row * d + c] = acc;
+                acc = fma((double)coef[q].x, (double)X[(int64_t)esu[q].y * d + c], acc);
+            Y[row * d + c] = (float)acc;
         }
     }
 }

@@ -1,0 +1,351 @@
+"""Every segmented-sum path of the MF step over stated segment layouts, bit for bit against an exact integer step.
+
+tests/segment_layouts.py has the layouts (segments aligned with, one entry past and one entry short of every run and
+chunk size of the library; hot rows through many chunks and through several blocks of the two-level edge chains; last
+chunks of one entry) and `exact_step`, the int64 restatement of one SGD step that tests/test_host_segment_layouts.py ties
+to oracle.bpr_mf_numpy.mf_sgd_step.  The inputs are chosen (small-integer tables, reg 0, power-of-two learning rate, hinge
+or squared loss) and CHECKED (`assert_exact_domain`, for every case before it runs) so that every partial sum in any
+order is an fp32 number: a path that adds every entry exactly once returns the reference's bits, and one entry dropped,
+doubled or sent to the wrong row - which the round-off tolerance of the random-id tests hides in a hot row - does not.
+Every comparison below is torch.equal on whole tables, untouched rows included; there is no tolerance for the MF paths.
+
+Paths: the phase kernels (k_fwd, k_item_grad_chunked / k_item_edges - also through item_grad_data and with FM's item bias
+-, k_item_grad_sorted, k_item_grad_atomic, k_user), sgd_step in the modes atomic / sorted / chunked (k_user_chunked /
+k_user_edges for rows of at most 4 floats per lane), the staged step in its six reachable forms (three launches x dense /
+sparse; four launches x dense / sparse x edge chains link by link / in two levels) from the sorted and from the
+partitioned plan, and the one-workgroup small-batch epoch.  The last part runs LightGCN's products - segsum_rows with
+its longer runs for wide rows - over graphs whose user rows follow the same layouts, at the tolerance of
+test_gpu_lightgcn.py (their coefficients 1 / sqrt(deg deg) are no dyadic rationals).
+
+Each test prints the number of (layout, d, path) cases it compared.
+"""
+import numpy as np
+import pytest
+import torch
+
+import segment_layouts as S
+from oracle import lightgcn_numpy as LG
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+STAGED_ENV = ("DAISY_STAGED_MERGE", "DAISY_STAGED_SPARSE", "DAISY_EDGE_BLOCKS")
+# the six reachable forms of the staged step (the three-launch form keeps its edge chains link by link)
+FUSED_FORMS = [dict(DAISY_STAGED_MERGE="1", DAISY_STAGED_SPARSE=sp) for sp in "01"] + \
+              [dict(DAISY_STAGED_MERGE="0", DAISY_STAGED_SPARSE=sp, DAISY_EDGE_BLOCKS=eb) for sp in "01" for eb in "01"]
+MODES = ("atomic", "sorted", "chunked")
+
+_BATCHES = {}          # (family, loss) -> [(name, u, i, j, U, I)]: the batches do not depend on d
+
+
+def _dev(x, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+    return t if dtype is None else t.to(dtype)
+
+
+def _batches(family, cases, loss):
+    key = (family, loss)
+    if key not in _BATCHES:
+        out = []
+        for k, case in enumerate(cases):
+            u, i, j, U, I = S.make_batch(case, loss, seed=k)
+            out.append((case[0], _dev(u), _dev(i), _dev(j), U, I))
+        _BATCHES[key] = out
+    return _BATCHES[key]
+
+
+def _form_name(env):
+    return "fused[" + ",".join(f"{k.split('_')[-1].lower()}={v}" for k, v in env.items()) + "]"
+
+
+class Failures(list):
+    """collects mismatches so that one run names every (case, path) that misses, not the first only"""
+
+    def same(self, got, want, what):
+        if torch.equal(got, want):
+            return
+        bad = (got != want).reshape(got.shape[0], -1).any(1).nonzero().reshape(-1)
+        r = int(bad[0])
+        self.append(f"{what}: {len(bad)} rows differ; row {r}: got {got[r].reshape(-1)[:4].tolist()} want {want[r].reshape(-1)[:4].tolist()}")
+
+    def loss(self, got, want, what):
+        if float(got) != float(want):
+            self.append(f"{what}: loss {float(got)!r} != {float(want)!r}")
+
+    def done(self, n_cases, label):
+        print(f"\nsegment layouts: {label}: {n_cases} (layout, d, path) cases")
+        assert not self, f"{len(self)} mismatches, the first of them:\n" + "\n".join(self[:12])
+
+
+class World:
+    """The tables, batches, exact results and the context of one (family of cases, d, loss); everything on the device."""
+
+    def __init__(self, family, cases, B, d, loss, biases=False):
+        from daisyrec_amd import ops
+        self.ops, self.d, self.loss, self.B, self.lr = ops, d, loss, B, S.LR[loss]
+        self.batches = _batches(family, cases, loss)
+        self.U, self.I = max(b[4] for b in self.batches), max(b[5] for b in self.batches)
+        P0, Q0 = S.int_tables(np.random.default_rng(1000 + d), self.U, self.I, d, loss)
+        self.P0, self.Q0 = _dev(P0), _dev(Q0)
+        Pi, Qi = self.P0.to(torch.int64), self.Q0.to(torch.int64)
+        self.bias0 = [_dev(x) for x in S.make_biases(self.U, self.I, d)] if biases else None
+        self.ref = []
+        for name, u, i, j, _, _ in self.batches:
+            st = S.exact_step(Pi, Qi, u, i, j, loss, self.lr, biases=self.bias0, device=DEV)
+            S.assert_exact_domain(st)
+            self.ref.append(dict(loss=float(st.loss), urows=st.urows, irows=st.irows, Pn=st.P_rows_new(), Qn=st.Q_rows_new(),
+                                 gP=st.gP.to(torch.float32), gQ=st.gQ.to(torch.float32), gb=st.g_i_bias.to(torch.float32)))
+        self.ctx = ops.BprContext(B, d, self.U, self.I)
+        self.ctx.set_pointwise(loss == S.SL)
+        self.P, self.Q = self.P0.clone(), self.Q0.clone()
+        self.sl = torch.zeros(1, dtype=torch.float64, device=DEV)
+
+    def close(self):
+        self.ctx.close()
+
+    def reset(self):
+        self.P.copy_(self.P0)
+        self.Q.copy_(self.Q0)
+        self.sl.zero_()
+
+    def expected(self, k):
+        r = self.ref[k]
+        return (self.P0.clone().index_copy_(0, r["urows"], r["Pn"]), self.Q0.clone().index_copy_(0, r["irows"], r["Qn"]))
+
+    def dense(self, k, key, rows, n):
+        r = self.ref[k]
+        return S.ExactStep.dense(r[rows], r[key], n)
+
+    def step(self, k, mode, fails, what):
+        """one sgd_step on batch k from the pristine tables: loss, P, Q (untouched rows included), gQ back at zero"""
+        name, u, i, j, _, _ = self.batches[k]
+        self.reset()
+        self.ctx.set_batch(u, i, j, validate=False)
+        self.ctx.sgd_step(self.P, self.Q, self.lr, 0.0, 0.0, loss_type=self.loss, item_mode=self.ops.ITEM_MODES[mode],
+                          step_loss=self.sl, accumulate=False)
+        self.check_step(k, fails, f"{name} {what}")
+
+    def check_step(self, k, fails, what, exp=None):
+        expP, expQ = exp if exp is not None else self.expected(k)
+        fails.loss(self.sl[0], self.ref[k]["loss"], what)
+        fails.same(self.P, expP, what + " P")
+        fails.same(self.Q, expQ, what + " Q")
+        if bool(self.ctx.gQ.any()):
+            fails.append(f"{what}: ctx.gQ is not all zero after the step")
+
+
+def _set_env(monkeypatch, env):
+    for k in STAGED_ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+WORLD_PARAMS = [(d, S.HL) for d in S.D_ALL] + [(d, S.SL) for d in S.D_SL]
+
+
+@pytest.fixture(scope="module", params=WORLD_PARAMS, ids=lambda p: f"{p[0]}-{'HL' if p[1] == S.HL else 'SL'}")
+def world(request):
+    """B = 4096 (8192 item entries, 4096 with the point-wise loss): one context per (d, loss), reused across the layouts"""
+    d, loss = request.param
+    w = World("main", S.main_cases(loss == S.SL), S.B_MAIN, d, loss)
+    yield w
+    w.close()
+
+
+def test_phase_kernels(world):
+    """set_batch, forward, then the item gradient by item_grad_data (chunked), item_grad (sorted, atomic, chunked) and the
+    user gradient by user_grad: the exact gradients, and the loss from finalize"""
+    w, ctx, fails = world, world.ctx, Failures()
+    gP = torch.zeros(w.U, w.d, device=DEV)
+    n = 0
+    for k, (name, u, i, j, _, _) in enumerate(w.batches):
+        w.reset()
+        want_gQ, want_gP = w.dense(k, "gQ", "irows", w.I), w.dense(k, "gP", "urows", w.U)
+        ctx.set_batch(u, i, j, validate=False)
+        ctx.forward(w.P, w.Q, loss_type=w.loss)
+        ctx.finalize(0.0, 0.0, step_loss=w.sl, accumulate=False)
+        fails.loss(w.sl[0], w.ref[k]["loss"], f"{name} forward")
+        ctx.gQ.zero_()
+        ctx.item_grad_data(w.P, w.Q, w.ops.ITEM_MODES["chunked"])
+        fails.same(ctx.gQ, want_gQ, f"{name} item_grad_data gQ")
+        for mode in ("sorted", "atomic", "chunked"):
+            ctx.gQ.zero_()
+            ctx.item_grad(w.P, w.Q, 0.0, 0.0, w.ops.ITEM_MODES[mode])
+            fails.same(ctx.gQ, want_gQ, f"{name} item_grad[{mode}] gQ")
+        gP.zero_()
+        ctx.user_grad(w.P, w.Q, 0.0, 0.0, gP)
+        fails.same(gP, want_gP, f"{name} user_grad gP")
+        fails.same(w.P, w.P0, f"{name} phases left P")
+        fails.same(w.Q, w.Q0, f"{name} phases left Q")
+        n += 5
+    ctx.gQ.zero_()
+    fails.done(n, f"phases d={w.d} loss={w.loss}")
+
+
+@pytest.mark.parametrize("d", S.D_ALL)
+def test_phase_item_bias_gradient(d):
+    """FM's biases attached (integers): the scores carry them, and the chunked item gradient also yields the exact
+    g_i_bias - the per-item sum of the coefficients rides along the same runs, slots and edge chains"""
+    w = World("main", S.main_cases(False), S.B_MAIN, d, S.HL, biases=True)
+    ctx, fails = w.ctx, Failures()
+    bu, bi, b0 = (x.clone() for x in w.bias0)
+    g_bu, g_bi, g_b0 = torch.zeros(w.U, device=DEV), torch.zeros(w.I, device=DEV), torch.zeros(1, device=DEV)
+    ctx.set_bias(bu, bi, b0, g_bu, g_bi, g_b0)
+    for k, (name, u, i, j, _, _) in enumerate(w.batches):
+        ctx.set_batch(u, i, j, validate=False)
+        ctx.forward(w.P, w.Q, loss_type=w.loss)
+        ctx.finalize(0.0, 0.0, step_loss=w.sl, accumulate=False)
+        fails.loss(w.sl[0], w.ref[k]["loss"], f"{name} forward with biases")
+        ctx.gQ.zero_()
+        g_bi.zero_()
+        ctx.item_grad_data(w.P, w.Q, w.ops.ITEM_MODES["chunked"])
+        fails.same(ctx.gQ, w.dense(k, "gQ", "irows", w.I), f"{name} item_grad_data gQ with biases")
+        fails.same(g_bi, w.dense(k, "gb", "irows", w.I), f"{name} g_i_bias")
+    ctx.gQ.zero_()
+    w.close()
+    fails.done(len(w.batches), f"item bias d={d}")
+
+
+def test_sgd_step_modes(world):
+    """sgd_step in the modes atomic, sorted and chunked"""
+    fails = Failures()
+    for k in range(len(world.batches)):
+        for mode in MODES:
+            world.step(k, mode, fails, mode)
+    fails.done(len(MODES) * len(world.batches), f"sgd_step d={world.d} loss={world.loss}")
+
+
+def test_staged_step_forms(world, monkeypatch):
+    """sgd_step in mode fused in its six forms, then the same batches served from a partitioned plan (TrainIndex,
+    EpochPlan.build_indexed with one batch, fit_epoch_sgd) in the form the library picks by itself"""
+    w, fails, ops = world, Failures(), world.ops
+    exp = [w.expected(k) for k in range(len(w.batches))] if w.d <= 128 else None
+    for env in FUSED_FORMS:
+        _set_env(monkeypatch, env)
+        for k in range(len(w.batches)):
+            name = w.batches[k][0]
+            w.reset()
+            w.ctx.set_batch(*w.batches[k][1:4], validate=False)
+            w.ctx.sgd_step(w.P, w.Q, w.lr, 0.0, 0.0, loss_type=w.loss, item_mode=ops.ITEM_MODES["fused"], step_loss=w.sl,
+                           accumulate=False)
+            w.check_step(k, fails, f"{name} {_form_name(env)}", exp[k] if exp else None)
+    _set_env(monkeypatch, {})
+    plan = ops.EpochPlan(w.B, w.U, w.I)
+    for k, (name, u, i, j, _, _) in enumerate(w.batches):
+        tri = torch.stack([u, i, j], 1).contiguous()
+        index = ops.TrainIndex(tri, w.U, w.I, pointwise=(w.loss == S.SL))
+        plan.build_indexed(index, w.B)
+        assert plan.num_batches == 1
+        w.reset()
+        w.ctx.fit_epoch_sgd(plan, w.P, w.Q, w.lr, 0.0, 0.0, loss_type=w.loss, item_mode=ops.ITEM_MODES["fused"], step_losses=w.sl)
+        w.check_step(k, fails, f"{name} fused[partitioned plan]", exp[k] if exp else None)
+        index.close()
+    plan.close()
+    fails.done((len(FUSED_FORMS) + 1) * len(w.batches), f"staged step d={w.d} loss={w.loss}")
+
+
+@pytest.mark.parametrize("d", S.D_ALL)
+def test_small_batch_epoch(d):
+    """B in {1, 2, 129, 256}: a one-batch sorted plan through fit_epoch_sgd(fused) - the persistent workgroup of
+    bpr_small.hip wherever the rows fit its LDS, the staged step otherwise"""
+    from daisyrec_amd import ops
+    fails, n = Failures(), 0
+    for B in S.B_SMALL:
+        w = World(f"small-{B}", S.small_cases(B), B, d, S.HL)
+        plan = ops.EpochPlan(B, w.U, w.I)
+        for k, (name, u, i, j, _, _) in enumerate(w.batches):
+            plan.build(torch.stack([u, i, j], 1).contiguous(), B)
+            assert plan.num_batches == 1
+            w.reset()
+            w.ctx.fit_epoch_sgd(plan, w.P, w.Q, w.lr, 0.0, 0.0, loss_type=w.loss, item_mode=ops.ITEM_MODES["fused"], step_losses=w.sl)
+            w.check_step(k, fails, f"B={B} {name} small epoch")
+            n += 1
+        plan.close()
+        w.close()
+    fails.done(n, f"small-batch epoch d={d}")
+
+
+@pytest.mark.parametrize("d", S.D_OFF_GRID)
+def test_sizes_off_the_grid(d, monkeypatch):
+    """B in {1, 129, 2049} with the period nearest to B: one entry, or one run, in the last chunk - every step path"""
+    fails, n = Failures(), 0
+    for B in S.OFF_GRID:
+        w = World(f"off-grid-{B}", S.off_grid_cases(B), B, d, S.HL)
+        for k in range(len(w.batches)):
+            _set_env(monkeypatch, {})
+            for mode in MODES + ("fused",):
+                w.step(k, mode, fails, f"B={B} {mode}")
+            for env in FUSED_FORMS:
+                _set_env(monkeypatch, env)
+                w.step(k, "fused", fails, f"B={B} {_form_name(env)}")
+            n += len(MODES) + 1 + len(FUSED_FORMS)
+        w.close()
+    fails.done(n, f"off the grid d={d}")
+
+
+@pytest.mark.parametrize("d", S.D_LONG)
+def test_long_chains(d, monkeypatch):
+    """B = 32768: one item with about 65 000 entries and one user with about 32 000 samples - chains of edge records
+    through hundreds of `whole` chunks and several kEdgeBlock blocks at every chunk size; the phase kernels (chunked),
+    then the four-launch staged step with its chains link by link and in two levels"""
+    w = World("long", S.long_cases(), S.B_LONG, d, S.HL)
+    fails = Failures()
+    forms = [dict(DAISY_STAGED_MERGE="0", DAISY_EDGE_BLOCKS=eb) for eb in "01"]
+    for k in range(len(w.batches)):
+        _set_env(monkeypatch, {})
+        w.step(k, "chunked", fails, "chunked")
+        for env in forms:
+            _set_env(monkeypatch, env)
+            w.step(k, "fused", fails, _form_name(env))
+    w.close()
+    fails.done((1 + len(forms)) * len(w.batches), f"long chains d={d}")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# LightGCN's products over the same layouts
+# ----------------------------------------------------------------------------------------------------------------------
+LG_LINKS = 8192
+LG_D = (64, 130, 160, 256, 300, 512)
+LG_LAYOUTS = [[f"period({p},{lead})" for lead in sorted({0, 1, p - 1})] for p in S.PERIODS[1:11]] + [["one", "long(1)"]]
+
+
+def _layout_graph(lens):
+    """user u is linked to the items (start_u + t) mod I for t < lens[u], I larger than the longest segment: the user
+    rows of the entry list follow the layout exactly, the item rows follow from it"""
+    lens = np.asarray(lens, np.int64)
+    I = int(lens.max()) + 37
+    gu = np.repeat(np.arange(len(lens)), lens)
+    start = np.cumsum(lens) - lens
+    t = np.arange(len(gu)) - start[gu]
+    gi = (start[gu] * 7 + t) % I
+    return gu, gi, len(lens), I
+
+
+@pytest.mark.parametrize("names", LG_LAYOUTS, ids=lambda n: n[0].split(",")[0].replace("(", ""))
+def test_lightgcn_products_over_the_layouts(names):
+    """graph.spmm (segsum_rows: the default run for rows of up to 8 floats per lane, runs of 4 for wider ones) and the
+    row-owner product of set_reproducible(True) against the fp64 CSR product.  X holds integers in [1, 4]: nothing
+    cancels, so a missing term of a row of degree g <= 4096 moves the row by about 1 / g - far above the tolerance of
+    test_spmm_shapes_long_and_short_rows (rtol 2e-5, atol 2e-6), which is kept; the two modes also agree with each other
+    at that tolerance.  (`one` is a row of 8192 entries: the row owners used to add it in one fp32 accumulator and came
+    out 5.9e-5 of the row away from the fp64 product - nothing missing, g / 2 ulps of round-off; k_lg_spmm_owner now
+    keeps its running sum in a double.)"""
+    from daisyrec_amd import ops
+    n = 0
+    for name in names:
+        gu, gi, U, I = _layout_graph(S.named(LG_LINKS, name))
+        assert len(np.unique(gu * I + gi)) == LG_LINKS
+        rng = np.random.default_rng(len(name) + U)
+        X = rng.integers(1, 5, (U + I, max(LG_D))).astype(np.float32)
+        want = LG.spmm(LG.norm_adj_csr(gu, gi, U, I), X.astype(np.float64))          # columns are independent: d <= 512 slices it
+        graph = ops.LgcnGraph(_dev(gu), _dev(gi), U, I)
+        for d in LG_D:
+            Xd, got = _dev(X[:, :d]), {}
+            for repro in (False, True):
+                graph.set_reproducible(repro)
+                got[repro] = graph.spmm(Xd).cpu().numpy()
+                np.testing.assert_allclose(got[repro], want[:, :d], rtol=2e-5, atol=2e-6, err_msg=f"{name} d={d} reproducible={repro}")
+                n += 1
+            np.testing.assert_allclose(got[False], got[True], rtol=2e-5, atol=2e-6, err_msg=f"{name} d={d} chunked against row owners")
+        graph.close()
+    print(f"\nsegment layouts: lightgcn {names}: {n} (layout, d, path) cases")
