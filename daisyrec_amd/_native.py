@@ -273,6 +273,10 @@ SIGNATURES = {
     "daisy_prep_process": (C.c_int, [_p, _p, _p, _p, _i64, _i32, C.c_double, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p,
                                      C.POINTER(_i64), _p]),
     "daisy_split_ids": (C.c_int, [_i32, _p, _p, _i64, _i64, C.c_double, C.c_double, _u64, _u64, _p, _p, C.POINTER(_i64), _p]),
+    "daisy_history_counts": (C.c_int, [_p, _i64, _i64, _p, _p, _p, C.POINTER(_i64), _p]),
+    "daisy_history_fill": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "daisy_history_csr": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, C.POINTER(_i64), _p]),
+    "daisy_history_first_seen": (C.c_int, [_p, _i64, _i64, _p, C.POINTER(_i64), _p]),
     "daisy_ngcf_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "daisy_ngcf_layer_forward": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _u64,
                                            _i32, _p]),

@@ -20,8 +20,16 @@ METRICS_NAMES = ("metrics_name_config", "calc_ranking_results", "Metric", "Cover
 SPLITTER_NAMES = ("TestSplitter", "ValidationSplitter", "split_test", "split_validation")
 
 
-def install(sampler=False, front_end=False, metrics=False, prep=False):
+# what install(history=True) rebinds in daisy.utils.utils (and AEDataset in daisy.utils.dataset)
+HISTORY_NAMES = ("get_history_matrix", "get_inter_matrix")
+
+
+def install(sampler=False, front_end=False, metrics=False, prep=False, history=False):
     """Patch `daisy.model.MFRecommender.MF` (and the other mirrored recommenders) in place.
+    history: also `daisy.utils.utils.get_history_matrix` / `get_inter_matrix` and `daisy.utils.dataset.AEDataset` (the padded
+    histories of multi-vae, the interaction matrix of lightgcn / ngcf and the AE loader's users from the device instead of
+    Python loops over the rows).  Like front_end: call before the driver module is imported
+    (test.py:22-23 binds the names at import).  Without it both modules' names are left untouched.
     prep: also `daisy.utils.loader.Preprocessor` and `daisy.utils.splitter`'s `TestSplitter`, `ValidationSplitter`,
     `split_test`, `split_validation` (dedup, k-core, encoding, time sort and every split on the device instead of Python
     loops over rows and users; DESIGN.md section 21 lists the deviations).  Like front_end: call before the driver module
@@ -119,4 +127,12 @@ def install(sampler=False, front_end=False, metrics=False, prep=False):
         ref_u = importlib.import_module("daisy.utils.utils")
         ref_u.get_ur, ref_u.get_ir = U.get_ur, U.get_ir
         ref_u.build_candidates_set = U.build_candidates_set
+    if history:
+        from .utils import dataset as D, utils as U
+
+        ref_u = importlib.import_module("daisy.utils.utils")
+        for name in HISTORY_NAMES:
+            setattr(ref_u, name, getattr(U, name))
+        ref_d = importlib.import_module("daisy.utils.dataset")
+        ref_d.AEDataset = D.AEDataset
     return MF

@@ -108,8 +108,11 @@ class NGCF(GeneralRecommender):
         """get_norm_adj_mat (:124-144) on the device, built once (the LightGCN graph)."""
         if self._graph is None:
             m = self.interaction_matrix.tocoo()
-            users = torch.as_tensor(np.ascontiguousarray(m.row)).to(self.device)
-            items = torch.as_tensor(np.ascontiguousarray(m.col)).to(self.device)
+            if isinstance(m.row, torch.Tensor):     # utils.get_inter_matrix's device columns: no scipy, no second upload
+                users, items = m.row.to(self.device), m.col.to(self.device)
+            else:
+                users = torch.as_tensor(np.ascontiguousarray(m.row)).to(self.device)
+                items = torch.as_tensor(np.ascontiguousarray(m.col)).to(self.device)
             self._graph = ops.LgcnGraph(users, items, self.user_num, self.item_num)
             self._graph.set_reproducible(self.item_mode == "sorted")
         return self._graph

@@ -39,8 +39,13 @@ class VAECF(AERecommender):
         self.user_num = config["user_num"]
         self.item_num = config["item_num"]
 
-        self.history_item_id = config["history_item_id"].to(self.device)
-        self.history_item_value = config["history_item_value"].to(self.device)
+        # config['history_csr'] (utils.history_csr: the users' rows as a device CSR, built from the interactions alone):
+        # the padded pair is then optional
+        self.history_csr = config.get("history_csr")
+        hid = config.get("history_item_id") if self.history_csr is not None else config["history_item_id"]
+        hval = config.get("history_item_value") if self.history_csr is not None else config["history_item_value"]
+        self.history_item_id = None if hid is None else hid.to(self.device)
+        self.history_item_value = None if hval is None else hval.to(self.device)
         self.update = 0
 
         self.encode_layer_dims = [self.item_num] + self.layers + [self.lat_dim]
@@ -85,6 +90,12 @@ class VAECF(AERecommender):
     def _csr(self):
         """The user rows of R on the device (ops.vae_history_csr), rebuilt when the history tensors change; also the
         rows' entry counts on the host (the per-batch entry counts the kernels are given)."""
+        if self.history_csr is not None:
+            key = ("csr", id(self.history_csr))
+            if self._csr_cache is None or self._csr_cache[0] != key:
+                csr = self._checked_csr(self.history_csr)
+                self._csr_cache = (key, csr, (csr[0][1:] - csr[0][:-1]).cpu())
+            return self._csr_cache[1], self._csr_cache[2]
         key = (id(self.history_item_id), id(self.history_item_value))
         if self._csr_cache is None or self._csr_cache[0] != key:
             hid = self.history_item_id.to(self.device)
@@ -94,8 +105,44 @@ class VAECF(AERecommender):
             self._csr_cache = (key, csr, lens)
         return self._csr_cache[1], self._csr_cache[2]
 
+    def _checked_csr(self, given):
+        """config['history_csr'] = (row_ptr int64 [user_num + 1], col int32 [nnz], val float32 [nnz][, L]) as
+        utils.history_csr returns it: shapes, dtypes, row_ptr and the column range are checked before a kernel reads it."""
+        if not isinstance(given, (tuple, list)) or len(given) not in (3, 4):
+            raise TypeError("config['history_csr']: expected (row_ptr, col, val) or (row_ptr, col, val, L)")
+        row_ptr, col, val = (torch.as_tensor(t).to(self.device).contiguous() for t in given[:3])
+        if row_ptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
+            raise TypeError(f"config['history_csr']: expected int64 / int32 / float32 tensors, got {row_ptr.dtype}, {col.dtype}, "
+                            f"{val.dtype}")
+        if row_ptr.dim() != 1 or row_ptr.numel() != int(self.user_num) + 1 or col.dim() != 1 or val.shape != col.shape:
+            raise ValueError(f"config['history_csr']: expected row_ptr [{int(self.user_num) + 1}] and col / val [nnz], got "
+                             f"{tuple(row_ptr.shape)}, {tuple(col.shape)}, {tuple(val.shape)}")
+        if int(row_ptr[0]) != 0 or int(row_ptr[-1]) != col.numel() or bool((row_ptr[1:] < row_ptr[:-1]).any()):
+            raise ValueError(f"config['history_csr']: row_ptr must ascend from 0 to nnz = {col.numel()}")
+        if col.numel() and (int(col.min()) < 0 or int(col.max()) >= int(self.item_num)):
+            raise IndexError(f"index out of range: history item ids must lie in [0, {int(self.item_num)})")
+        return row_ptr, col, val
+
+    def get_user_rating_matrix(self, user):
+        """AbstractRecommender.py:147-158 -> [B, item_num]; with config['history_csr'] the asked rows are densified from
+        the CSR (the same rows: the CSR is what index_put_ leaves of the padded pair)."""
+        if self.history_csr is None:
+            return super().get_user_rating_matrix(user)
+        (row_ptr, col, val), _ = self._csr()
+        rows = torch.as_tensor(user).to(self.device).long().reshape(-1)
+        self._check_users(rows)
+        out = torch.zeros(rows.numel(), self.item_num, dtype=torch.float32, device=self.device)
+        lens = row_ptr[rows + 1] - row_ptr[rows]
+        total = int(lens.sum()) if rows.numel() else 0
+        if total:
+            which = torch.repeat_interleave(torch.arange(rows.numel(), device=self.device), lens)
+            begin = torch.cumsum(lens, 0) - lens
+            src = row_ptr[rows][which] + (torch.arange(total, device=self.device) - begin[which])
+            out[which, col[src].long()] = val[src]
+        return out
+
     def _check_users(self, users):
-        U = int(self.history_item_id.shape[0])
+        U = int(self.user_num) if self.history_csr is not None else int(self.history_item_id.shape[0])
         if users.numel() and (int(users.min()) < 0 or int(users.max()) >= U):
             raise IndexError(f"index {int(users.max()) if int(users.max()) >= U else int(users.min())} is out of bounds "
                              f"for dimension 0 with size {U}")

@@ -1979,3 +1979,84 @@ def split_ids(method, n, user_code=None, user_num=0, timestamp=None, size=0.5, s
                               int(seed) & (2 ** 64 - 1), int(fold), _ptr(train, torch.int64, "train"),
                               _ptr(test, torch.int64, "test"), counts, _stream()))
     return train[:counts[0]], test[:counts[1]]
+
+
+# ---- history matrix, its CSR and first-seen order (csrc/history.hip) -------------------------------------
+def _codes(t, num, name, validate):
+    """an int32 device column of dense codes; validate: one device min / max against [0, num) (the kernels index with them)"""
+    t = t.contiguous()
+    if validate and t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi >= int(num):
+            raise IndexError(f"{name}: index {hi if hi >= int(num) else lo} is out of bounds for size {int(num)}")
+    return t
+
+
+def history_counts(row, row_num, validate=True):
+    """daisy_history_counts on an int32 device column of row codes -> (history_len int64 [row_num], L, order int32 [n],
+    start int64 [row_num + 1]); order / start are what history_fill reads.  L is the one word the host reads."""
+    row = _codes(row, row_num, "row", validate)
+    n, dev = row.numel(), row.device
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    start = torch.empty(int(row_num) + 1, dtype=torch.int64, device=dev)
+    hlen = torch.empty(int(row_num), dtype=torch.int64, device=dev)
+    longest = C.c_int64(0)
+    with torch.cuda.device(dev):
+        check(lib.daisy_history_counts(_ptr(row, torch.int32, "row"), n, int(row_num), _ptr(order, torch.int32, "order"),
+                                       _ptr(start, torch.int64, "start"), _ptr(hlen, torch.int64, "history_len"),
+                                       C.byref(longest), _stream()))
+    return hlen, int(longest.value), order, start
+
+
+def history_fill(order, start, col, val, row_num, L):
+    """daisy_history_fill -> (history_matrix int64 [row_num, L], history_value float32 [row_num, L]); order / start from
+    history_counts of the same frame, col int32 [n] (copied, never an index), val float64 [n] or None for all ones.
+    Every cell is written once by the kernel: the outputs are allocated uninitialised."""
+    n, dev = order.numel(), order.device
+    if col.numel() != n or (val is not None and val.numel() != n):
+        raise ValueError(f"history_fill: columns of different lengths ({n} rows)")
+    if start.numel() != int(row_num) + 1:
+        raise ValueError(f"history_fill: start has {start.numel()} entries, row_num + 1 = {int(row_num) + 1} expected")
+    hid = torch.empty((int(row_num), int(L)), dtype=torch.int64, device=dev)
+    hval = torch.empty((int(row_num), int(L)), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.daisy_history_fill(_ptr(order, torch.int32, "order"), _ptr(start, torch.int64, "start"),
+                                     _ptr(col.contiguous(), torch.int32, "col"),
+                                     _ptr(None if val is None else val.contiguous(), torch.float64, "val"), n, int(row_num),
+                                     int(L), _ptr(hid, torch.int64, "history_matrix"), _ptr(hval, torch.float32, "history_value"),
+                                     _stream()))
+    return hid, hval
+
+
+def history_csr(row, col, val, row_num, col_num, validate=True):
+    """daisy_history_csr on int32 device code columns (val float64 [n] or None for all ones) -> (row_ptr int64
+    [row_num + 1], col int32 [nnz], val float32 [nnz], L): byte for byte what vae_history_csr makes of the padded pair of
+    the same frame, without the padded pair."""
+    row, col = _codes(row, row_num, "row", validate), _codes(col, col_num, "col", validate)
+    n, dev = row.numel(), row.device
+    if col.numel() != n or (val is not None and val.numel() != n):
+        raise ValueError(f"history_csr: columns of different lengths ({n} rows)")
+    row_ptr = torch.empty(int(row_num) + 1, dtype=torch.int64, device=dev)
+    out_col = torch.empty(n, dtype=torch.int32, device=dev)
+    out_val = torch.empty(n, dtype=torch.float32, device=dev)
+    totals = (C.c_int64 * 2)()
+    with torch.cuda.device(dev):
+        check(lib.daisy_history_csr(_ptr(row, torch.int32, "row"), _ptr(col, torch.int32, "col"),
+                                    _ptr(None if val is None else val.contiguous(), torch.float64, "val"), n, int(row_num),
+                                    int(col_num), _ptr(row_ptr, torch.int64, "row_ptr"), _ptr(out_col, torch.int32, "col"),
+                                    _ptr(out_val, torch.float32, "val"), totals, _stream()))
+    nnz = int(totals[0])
+    return row_ptr, out_col[:nnz].clone(), out_val[:nnz].clone(), int(totals[1])
+
+
+def history_first_seen(ids, id_num, validate=True):
+    """daisy_history_first_seen: the distinct values of an int32 device column (< id_num) in order of first appearance,
+    int64 (what pandas.unique returns)."""
+    ids = _codes(ids, id_num, "ids", validate)
+    n, dev = ids.numel(), ids.device
+    out = torch.empty(min(n, int(id_num)), dtype=torch.int64, device=dev)
+    count = C.c_int64(0)
+    with torch.cuda.device(dev):
+        check(lib.daisy_history_first_seen(_ptr(ids, torch.int32, "ids"), n, int(id_num), _ptr(out, torch.int64, "out"),
+                                           C.byref(count), _stream()))
+    return out[:count.value]

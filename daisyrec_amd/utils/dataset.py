@@ -51,6 +51,40 @@ class CandidatesDataset(Dataset):
         return torch.tensor(self.data[index][0]), torch.tensor(self.data[index][1])
 
 
+class AEDataset(Dataset):
+    """dataset.py:40-58: the distinct values of `train_set[yield_col]` in order of first appearance (what
+    `Series.unique()` returns), one per sample.  The order comes from the device (ops.history_first_seen: the first frame
+    position of every id, then a compaction in frame order); `.data` is the host int64 vector the reference holds -
+    `VAECF.fit` reads it from there.  Ids that are not small non-negative integers go through their dense codes first
+    (ops.prep_encode).  There is no CPU path."""
+
+    def __init__(self, train_set, yield_col='user'):
+        super().__init__()
+        ids = np.asarray(train_set[yield_col].values)
+        if ids.dtype.kind not in "iu":
+            raise TypeError(f"AEDataset: column {yield_col!r} has dtype {ids.dtype}; integer ids expected")
+        if not torch.cuda.is_available():
+            raise RuntimeError("daisyrec_amd.AEDataset needs a HIP device (no CPU fallback)")
+        n = ids.size
+        if n == 0:
+            self.data = np.zeros(0, dtype=np.int64)
+            return
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo >= 0 and hi < max(4 * n, 1 << 20):
+            codes = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).cuda()
+            first = ops.history_first_seen(codes, hi + 1, validate=False)
+        else:           # raw ids: rank them first, order the ranks, read the ids back
+            codes, tokens = ops.prep_encode(torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).cuda())
+            first = tokens[ops.history_first_seen(codes, tokens.numel(), validate=False)]
+        self.data = first.cpu().numpy().astype(np.int64, copy=False)
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, index):
+        return self.data[index]
+
+
 class DeviceTripleLoader:
     """HBM-resident triples + per-epoch device permutation (shuffle=True semantics:
     every epoch is a fresh uniform permutation; last batch partial)."""

@@ -75,3 +75,126 @@ def build_candidates_set(test_ur, train_ur, config, drop_past_inter=True):
     cands = ops.build_candidates(ip_te, it_te, ip_tr, it_tr, users, item_num, cand_num,
                                  int(config.get("seed", 2022))).cpu().numpy()
     return test_u, [[u, cands[k]] for k, u in enumerate(test_u)]
+
+
+# ---- get_history_matrix / get_inter_matrix (utils.py:87-144) ----------------------------------------------
+def _check_codes(ids, num, what):
+    """IndexError for an id outside [0, num), on the host and before any launch.  (The reference indexes numpy arrays
+    with them: too large an id raises there as well, a negative one wraps - refused here)"""
+    if ids.size:
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < 0 or hi >= int(num):
+            bad = hi if hi >= int(num) else lo
+            raise IndexError(f"index {bad} is out of bounds for axis 0 with size {int(num)} ({what} ids must lie in "
+                             f"[0, {int(num)}))")
+
+
+def _history_columns(df, config, row, use_config_value_name, what):
+    """The part of get_history_matrix before its loops (utils.py:91-105): the assertion, the row / column choice and
+    the value column; then the range check and the device columns (int32 codes, float64 values or None for ones)."""
+    assert row in df.columns, f'invalid name {row}: not in columns of history dataframe'
+    uid_name, iid_name = config['UID_NAME'], config['IID_NAME']
+    user_ids, item_ids = df[uid_name].values, df[iid_name].values
+    value_name = config['INTER_NAME'] if use_config_value_name else None
+    user_num, item_num = config['user_num'], config['item_num']
+    if row == 'user':
+        row_num, max_col_num = user_num, item_num
+        row_ids, col_ids = user_ids, item_ids
+    else:  # 'item'
+        row_num, max_col_num = item_num, user_num
+        row_ids, col_ids = item_ids, user_ids
+    row_ids, col_ids = np.asarray(row_ids), np.asarray(col_ids)
+    _check_codes(row_ids, row_num, row)
+    _check_codes(col_ids, max_col_num, "column")
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"daisyrec_amd.{what} needs a HIP device (no CPU fallback)")
+    dev = torch.device(config.get("device", "cuda"))
+    cols = None
+    if len(row_ids):
+        r = torch.from_numpy(np.ascontiguousarray(row_ids, dtype=np.int32)).to(dev)
+        c = torch.from_numpy(np.ascontiguousarray(col_ids, dtype=np.int32)).to(dev)
+        # values: float64 on the host (np.ones / the frame's column stored into a float64 matrix, utils.py:98,116), cast
+        # to float32 once on the device (torch.FloatTensor, utils.py:123)
+        v = None if value_name is None else torch.from_numpy(
+            np.ascontiguousarray(df[value_name].values, dtype=np.float64)).to(dev)
+        cols = (r, c, v)
+    return cols, int(row_num), int(max_col_num), dev
+
+
+def get_history_matrix(df, config, row='user', use_config_value_name=False):
+    """utils.py:87-123 without its two loops over the rows: (history_matrix int64 [R, L], history_value float32 [R, L],
+    history_len int64 [R]) as DEVICE tensors, cell for cell the reference's.  One stable sort by row code gives the order
+    inside a row; one kernel writes every cell once.  The padded pair costs R * L * 12 bytes: when that does not fit the
+    device's free memory a MemoryError says so - history_csr gives VAECF the same rows from the interactions alone."""
+    logger = config['logger']
+    cols, row_num, max_col_num, dev = _history_columns(df, config, row, use_config_value_name, "get_history_matrix")
+    if cols is None:
+        return (torch.zeros((row_num, 0), dtype=torch.int64, device=dev), torch.zeros((row_num, 0), dtype=torch.float32, device=dev),
+                torch.zeros(row_num, dtype=torch.int64, device=dev))
+    r, c, v = cols
+    history_len, col_num, order, start = ops.history_counts(r, row_num, validate=False)
+    if col_num > max_col_num * 0.2:
+        logger.info(f'Max value of {row}\'s history interaction records has reached: {col_num / max_col_num * 100:.4f}% of the total.')
+    need = row_num * col_num * 12
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if need > free:
+        raise MemoryError(f"get_history_matrix: the padded [{row_num}, {col_num}] pair needs {need} bytes, the device has "
+                          f"{free} free; use daisyrec_amd.utils.utils.history_csr (config['history_csr']), which is "
+                          "bounded by the interactions")
+    history_matrix, history_value = ops.history_fill(order, start, c, v, row_num, col_num)
+    return history_matrix, history_value, history_len
+
+
+def history_csr(df, config, row='user', use_config_value_name=False):
+    """The rows get_history_matrix's pair stands for under AERecommender.get_user_rating_matrix, as a device CSR and
+    without the padded pair: (row_ptr int64 [R + 1], col int32 [nnz], val float32 [nnz], L).  Byte for byte
+    ops.vae_history_csr of get_history_matrix's tensors; config['history_csr'] hands it to VAECF."""
+    cols, row_num, max_col_num, dev = _history_columns(df, config, row, use_config_value_name, "history_csr")
+    if cols is None:
+        return (torch.zeros(row_num + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(0, dtype=torch.float32, device=dev), 0)
+    r, c, v = cols
+    return ops.history_csr(r, c, v, row_num, max_col_num, validate=False)
+
+
+class DeviceInterMatrix:
+    """What get_inter_matrix returns here: the interaction frame as device columns, with the corner of scipy's COO
+    interface the recommenders read.  row / col int32 and data float64, in frame order, duplicates kept - as
+    sp.coo_matrix((data, (src, tar))) keeps them."""
+    format = "coo"
+
+    def __init__(self, row, col, data, shape):
+        self.row, self.col, self.data = row, col, data
+        self.shape = (int(shape[0]), int(shape[1]))
+
+    @property
+    def nnz(self):
+        return int(self.row.numel())
+
+    def tocoo(self):
+        return self
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+        return sp.coo_matrix((self.data.cpu().numpy(), (self.row.cpu().numpy(), self.col.cpu().numpy())), shape=self.shape)
+
+
+def get_inter_matrix(df, config, form='coo'):
+    """utils.py:125-144: the whole interaction matrix.  'coo': a DeviceInterMatrix (LightGCN / NGCF hand its columns to
+    the graph builder: no scipy build, one host-to-device copy); 'csr': the scipy CSR of the same frame."""
+    value_field = config['INTER_NAME']
+    src_field, tar_field = config['UID_NAME'], config['IID_NAME']
+    user_num, item_num = config['user_num'], config['item_num']
+    if form not in ('coo', 'csr'):
+        raise NotImplementedError(f'Sparse matrix format [{form}] has not been implemented...')
+    src, tar = np.asarray(df[src_field].values), np.asarray(df[tar_field].values)
+    data = np.asarray(df[value_field].values)
+    _check_codes(src, user_num, "user")
+    _check_codes(tar, item_num, "item")
+    if not torch.cuda.is_available():
+        raise RuntimeError("daisyrec_amd.get_inter_matrix needs a HIP device (no CPU fallback)")
+    dev = torch.device(config.get("device", "cuda"))
+    mat = DeviceInterMatrix(torch.from_numpy(np.ascontiguousarray(src, dtype=np.int32)).to(dev),
+                            torch.from_numpy(np.ascontiguousarray(tar, dtype=np.int32)).to(dev),
+                            torch.from_numpy(np.ascontiguousarray(data, dtype=np.float64)).to(dev), (user_num, item_num))
+    return mat if form == 'coo' else mat.to_scipy().tocsr()

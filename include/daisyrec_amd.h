@@ -1210,6 +1210,35 @@ int daisy_split_ids(int32_t method, const int32_t *user_code, const int64_t *tim
                     double one_minus_size, uint64_t seed, uint64_t fold, int64_t *train, int64_t *test, int64_t *counts_host,
                     daisy_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * get_history_matrix (daisy/utils/utils.py:87-123), the CSR that AERecommender.get_user_rating_matrix implies
+ * (AbstractRecommender.py:147-158) built without the padded pair, and pandas.unique's first-seen order (AEDataset,
+ * dataset.py:52): csrc/history.hip; DESIGN.md §23.  row / col: dense int32 codes in frame order, row < row_num,
+ * col < col_num (the caller checks the ranges); val fp64 [n] or NULL for all ones, cast to fp32 once.  Integer work
+ * apart from that cast, no floating-point atomic, two calls give the same bytes.  The entries allocate their own
+ * scratch and return with the stream drained.  1 <= n < 2^31, 1 <= row_num, col_num < 2^31.
+ * ---------------------------------------------------------------------- */
+/* history_len int64 [row_num] = the entries of every row; *longest_host (HOST) = the longest.  Also what the fill reads:
+ * order int32 [n] = the frame positions in a stable sort by row code, start int64 [row_num + 1] = where every row's
+ * entries begin in it. */
+int daisy_history_counts(const int32_t *row, int64_t n, int64_t row_num, int32_t *order, int64_t *start,
+                         int64_t *history_len, int64_t *longest_host, daisy_stream_t stream);
+/* history_matrix int64 [row_num, L], history_value fp32 [row_num, L]: row r = its entries in frame order from column 0,
+ * then zeros.  Every cell is written exactly once (no memset); cell indices are 64-bit.  order / start from
+ * daisy_history_counts, L >= the longest row. */
+int daisy_history_fill(const int32_t *order, const int64_t *start, const int32_t *col, const double *val, int64_t n,
+                       int64_t row_num, int64_t L, int64_t *history_matrix, float *history_value, daisy_stream_t stream);
+/* The rows of the rating matrix the padded pair stands for, as a CSR: row_ptr int64 [row_num + 1], out_col int32 and
+ * out_val fp32 (room for n each), columns ascending within a row.  Of a duplicated (row, col) the last in frame order
+ * stays; a row shorter than the longest loses its column 0 (the padding overwrites it); a row as long as the longest
+ * keeps it; entries whose fp32 value is 0 are dropped.  totals_host int64 [2] (HOST) = nnz, the longest row. */
+int daisy_history_csr(const int32_t *row, const int32_t *col, const double *val, int64_t n, int64_t row_num, int64_t col_num,
+                      int64_t *row_ptr, int32_t *out_col, float *out_val, int64_t *totals_host, daisy_stream_t stream);
+/* out int64 (room for min(n, id_num)): the distinct values of ids (int32 [n], < id_num) in order of first appearance;
+ * *count_host (HOST) = their number.  Integer atomicMin of the frame position per id, then a compaction in frame order. */
+int daisy_history_first_seen(const int32_t *ids, int64_t n, int64_t id_num, int64_t *out, int64_t *count_host,
+                             daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--native-prep", action="store_true",
                     help="also rebind daisy.utils.loader.Preprocessor and daisy.utils.splitter (k-core, encoding and every split "
                          "on the device)")
+    ap.add_argument("--native-history", action="store_true",
+                    help="also rebind daisy.utils.utils.get_history_matrix / get_inter_matrix and daisy.utils.dataset.AEDataset "
+                         "(multi-vae's histories, the graph models' interaction matrix: no Python row loops)")
     ap.add_argument("--extra-path", action="append", default=[],
                     help="directories put in front of sys.path (e.g. a stand-in for a package the image lacks)")
     ap.add_argument("rest", nargs=argparse.REMAINDER)
@@ -60,7 +63,8 @@ def main():
         sys.path.insert(0, os.path.abspath(extra))
 
     import daisyrec_amd.dropin as dropin
-    dropin.install(sampler=a.native_sampler, front_end=a.native_front_end, metrics=a.native_metrics, prep=a.native_prep)
+    dropin.install(sampler=a.native_sampler, front_end=a.native_front_end, metrics=a.native_metrics, prep=a.native_prep,
+                   history=a.native_history)
 
     os.chdir(os.path.abspath(a.daisy))                      # data_path etc. are relative (basic.yaml)
     sys.argv = [a.script] + rest
