@@ -185,6 +185,8 @@ SIGNATURES = {
     "daisy_fm_predict": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _p, _i64, _p, _p]),
     "daisy_fm_rank_topk": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _p, _i64, _i64, _i32, _p, _p, _p, _sz, _p]),
     "daisy_fm_full_rank": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _i32, _p, _p, _sz, _p]),
+    "daisy_full_rank_users_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "daisy_full_rank_users": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
     "daisy_neumf_ctx_create": (C.c_int, [C.POINTER(_p), _i64, _i32, _i32, _i32, _i64, _i64]),
     "daisy_neumf_ctx_destroy": (C.c_int, [_p]),
     "daisy_neumf_ctx_bytes": (_sz, [_p]),

@@ -117,3 +117,8 @@ class Item2Vec(GeneralRecommender):
         """:103-112 -> int64 [topk]"""
         Uemb, S = self._tables()
         return ops.mf_full_rank(Uemb, S, int(u), self.topk).cpu().numpy()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False):
+        """full ranking of many users over the user and item tables (MF.full_rank_users)"""
+        Uemb, S = self._tables()
+        return self._full_rank_users(Uemb, S, users, exclude, return_scores)

@@ -199,3 +199,8 @@ class LightGCN(GeneralRecommender):
         """:202-210 -> int64 [topk]"""
         ue, ie = self._restore()
         return ops.mf_full_rank(ue, ie, int(u), self.topk).cpu().numpy()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False):
+        """full ranking of many users over the propagated embeddings (MF.full_rank_users)"""
+        ue, ie = self._restore()
+        return self._full_rank_users(ue, ie, users, exclude, return_scores)

@@ -161,3 +161,10 @@ class MF(GeneralRecommender):
         """MFRecommender.py:126-133 -> int64 [topk]."""
         P, Q = self._tables()
         return ops.mf_full_rank(P, Q, int(u), self.topk, biases=self._biases()).cpu().numpy()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False):
+        """The full-ranking protocol for many users in two launches: device int64 [n, min(topk, I)],
+        each row what full_rank(u) returns once the items of the user's row of `exclude` (None, an (indptr, items)
+        device CSR of utils.user_csr, or a train_ur dict of sets) are dropped; -1 where a user has fewer eligible items."""
+        P, Q = self._tables()
+        return self._full_rank_users(P, Q, users, exclude, return_scores, biases=self._biases())

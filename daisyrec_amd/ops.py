@@ -703,6 +703,64 @@ def mf_full_rank(P, Q, u, topk, biases=None):
     return out
 
 
+FULL_RANK_TOPK_CAP = 128      # kFrTopkCap (csrc/rank_full.hip): the candidate buffers of a user tile live in LDS
+
+
+def _check_exclusion(indptr, items, user_num):
+    """ValueError unless (indptr, items) is a CSR over user_num rows whose rows are ascending (duplicates allowed):
+    what build_user_csr returns.  Two device reductions, each read back once."""
+    if indptr.dim() != 1 or items.dim() != 1 or indptr.numel() != user_num + 1:
+        raise ValueError(f"exclude: indptr has {indptr.numel()} entries, the user table has {user_num} rows "
+                         f"(expected {user_num + 1})")
+    nnz = items.numel()
+    steps_ok = bool(((indptr[1:] >= indptr[:-1]).all() & (indptr[0] == 0) & (indptr[-1] == nnz)).item())
+    if not steps_ok:
+        raise ValueError(f"exclude: indptr must rise from 0 to len(items) = {nnz}")
+    if nnz > 1:
+        inside = torch.ones(nnz + 1, dtype=torch.bool, device=items.device)
+        inside[indptr] = False                                  # position p starts a row: nothing to compare with
+        if bool(((items[1:] < items[:-1]) & inside[1:nnz]).any().item()):
+            raise ValueError("exclude: the items of a row must be ascending (utils.user_csr / ops.build_user_csr sort them)")
+
+
+def full_rank_users(P, Q, users, topk, exclude=None, biases=None, return_scores=False, item_slices=0, validate=True):
+    """Full ranking of many users in two launches (csrc/rank_full.hip): int64 [n, min(topk, I)] device
+    ids of the best items of ALL I by <P[u], Q[i]> (+ FM's biases), best first, equal scores by ascending id, without
+    the items of the user's row of `exclude` = (indptr int64 [U + 1], items int32 ascending per row), the device CSR of
+    build_user_csr.  A user with fewer eligible items than topk gets -1 (score -inf) in the remaining positions.
+    return_scores: (ids, float32 scores).  topk above FULL_RANK_TOPK_CAP raises ValueError.  validate: IndexError for a
+    user id outside [0, U), ValueError for an exclusion that is not such a CSR (one read-back each); False skips both -
+    the kernel then trusts the ids and indptr, and only ever compares row contents."""
+    U, I = int(P.shape[0]), int(Q.shape[0])
+    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1]:
+        raise ValueError(f"full_rank_users: P {tuple(P.shape)} and Q {tuple(Q.shape)} need the same column count")
+    users = torch.as_tensor(users).to(device=P.device, dtype=torch.int64).reshape(-1).contiguous()
+    n = users.numel()
+    topk = min(int(topk), I)                # as mf_full_rank: argsort(...)[:topk] truncates
+    ids = torch.empty(n, topk, dtype=torch.int64, device=P.device)
+    scores = torch.empty(n, topk, dtype=torch.float32, device=P.device) if return_scores else None
+    indptr = items = None
+    if exclude is not None:
+        indptr, items = exclude
+        if items.numel() == 0:              # (an empty tensor has no pointer to hand over)
+            items = torch.zeros(1, dtype=torch.int32, device=P.device)
+    if n and validate:
+        lo, hi = (int(x) for x in torch.stack([users.min(), users.max()]).tolist())
+        if lo < 0 or hi >= U:
+            raise IndexError(f"index {hi if hi >= U else lo} is out of bounds for the user table with {U} rows")
+        if exclude is not None:
+            _check_exclusion(indptr, exclude[1], U)
+    if n:
+        ws = _ws(lib.daisy_full_rank_users_workspace_bytes(n, I, topk, int(item_slices)), P.device)
+        bu, bi, b0 = _bias_ptrs(biases)
+        check(lib.daisy_full_rank_users(_ptr(P, torch.float32, "P"), _ptr(Q, torch.float32, "Q"), bu, bi, b0, P.shape[1], I,
+                                        _ptr(users, torch.int64, "users"), n, _ptr(indptr, torch.int64, "exclude indptr"),
+                                        _ptr(items, torch.int32, "exclude items"), topk, int(item_slices),
+                                        _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float32, "scores"),
+                                        _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return (ids, scores) if return_scores else ids
+
+
 def build_user_csr(users, items, user_num):
     """get_ur (utils.py:19-34) as a device CSR: (indptr int64[U+1], sorted items int32[n])."""
     n = users.numel()

@@ -441,6 +441,25 @@ int daisy_fm_full_rank(const float *P, const float *Q, const float *u_bias, cons
 int daisy_mf_full_rank(const float *P, const float *Q, int32_t d, int64_t item_num, int64_t u,
                        int32_t topk, int64_t *out_ids, void *workspace, size_t workspace_bytes,
                        daisy_stream_t stream);
+/* Full ranking of n users in two launches (csrc/rank_full.hip, additive to ABI 8): for every users[b] (int64 [n], any
+ * order, duplicates allowed) the topk items of all item_num by score <P[u], Q[i]> (+ (u_bias[u] + i_bias[i]) + bias[0]
+ * when the three are given: all NULL or none), best first, equal scores by ascending item id (-0.0 equals +0.0, a NaN
+ * score ranks first), without the items of the user's exclusion row.  P and Q are fp32 rows of d columns (the padded
+ * tables are fine: zero columns add zero).  The exclusion is a device CSR over all users - excl_indptr int64
+ * [user_num + 1], excl_items int32, ascending inside a row, duplicates allowed, exactly what daisy_build_user_csr
+ * returns (both NULL: nothing excluded).  Row contents are only compared, never used as an index: a row that breaks
+ * the contract may cost missed exclusions, never an out-of-bounds access; user ids and excl_indptr are the caller's
+ * to validate.  out_ids int64 [n, topk], out_scores fp32 [n, topk] or NULL; positions beyond a user's eligible items
+ * hold id -1 and score -inf.  1 <= topk <= min(item_num, 128): the candidate buffers live in LDS, and a larger topk is
+ * DAISY_ERR_ARG with the cap in the message, never a truncation.  item_slices: 0 picks the number of item slices per
+ * user tile from the tile counts, another value is clamped to the number of 128-item tiles; the result does not
+ * depend on it, bit for bit.  Nothing of size n * item_num is allocated: the workspace holds item_slices partial top-k
+ * lists per user.  Every argument is checked before the first HIP call. */
+size_t daisy_full_rank_users_workspace_bytes(int64_t n, int64_t item_num, int32_t topk, int32_t item_slices);
+int daisy_full_rank_users(const float *P, const float *Q, const float *u_bias, const float *i_bias, const float *bias,
+                          int32_t d, int64_t item_num, const int64_t *users, int64_t n, const int64_t *excl_indptr,
+                          const int32_t *excl_items, int32_t topk, int32_t item_slices, int64_t *out_ids,
+                          float *out_scores, void *workspace, size_t workspace_bytes, daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Uniform negative sampler (sampler.py:55-103, uniform branch :82-89)
