@@ -15,7 +15,8 @@ k_user_edges for rows of at most 4 floats per lane), the staged step in its six 
 sparse; four launches x dense / sparse x edge chains link by link / in two levels) from the sorted and from the
 partitioned plan, and the one-workgroup small-batch epoch.  The last part runs LightGCN's products - segsum_rows with
 its longer runs for wide rows - over graphs whose user rows follow the same layouts, at the tolerance of
-test_gpu_lightgcn.py (their coefficients 1 / sqrt(deg deg) are no dyadic rationals).
+test_gpu_lightgcn.py (their coefficients 1 / sqrt(deg deg) are no dyadic rationals on these graphs; on the biregular
+graphs of tests/dyadic_graphs.py they are, and tests/test_gpu_graph_products_exact.py compares the same products bit for bit).
 
 Each test prints the number of (layout, d, path) cases it compared.
 """
