@@ -266,6 +266,12 @@ SIGNATURES = {
     "daisy_knn_rank": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _i32, _p]),
     "daisy_knn_fit_bytes": (_sz, [_i64, _i64, _i32]),
     "daisy_knn_fits": (C.c_int, [_i64, _i64, _i32, _sz]),
+    "daisy_rank_f64_users_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "daisy_ease_full_rank_users": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _p, _p, _p]),
+    "daisy_slim_full_rank_users": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p]),
+    "daisy_knn_full_rank_users": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _i32, _p, _p, _i32,
+                                            _p]),
+    "daisy_psvd_full_rank_users": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p, _i32, _p, _p, _p]),
     "daisy_pop_fit": (C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
     "daisy_pop_rank": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
     "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),

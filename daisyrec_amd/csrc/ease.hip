@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "score_f64.h"
 #include "topk_f64.h"
 
 namespace daisy {
@@ -296,12 +297,7 @@ __global__ __launch_bounds__(kBlock) void k_ease_rank(const int64_t *__restrict_
     for (int64_t cidx = tid; cidx < C; cidx += kBlock) {
         const int64_t it = items ? items[b * C + cidx] : cidx;
         double s = 0.0;
-        if (it >= 0 && it < I) {
-            for (int64_t e = beg; e < end; ++e) {
-                const int64_t r = col[e];
-                if (r >= 0 && r < I) s = fma((double)val[e], W[r * I + it], s);
-            }
-        }
+        if (it >= 0 && it < I) s = ease_score(col, val, beg, end, W, I, it);
         row[cidx] = s;
     }
     if (!out_ids) return;

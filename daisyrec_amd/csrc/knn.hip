@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "score_f64.h"
 #include "topk_f64.h"
 
 namespace daisy {
@@ -227,17 +228,6 @@ __global__ __launch_bounds__(kBlock) void k_knn_select(const float *__restrict__
 }
 
 // ---- scores and top-k ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float knn_lookup(const int32_t *__restrict__ col, const float *__restrict__ val, int64_t beg,
-                                            int64_t end, int32_t r) {
-    while (beg < end) {                                 // columns ascend within a row
-        const int64_t mid = beg + (end - beg) / 2;
-        const int32_t c = col[mid];
-        if (c == r) return val[mid];
-        if (c < r) beg = mid + 1; else end = mid;
-    }
-    return 0.f;
-}
-
 // One workgroup per requested row of L, a thread per candidate column of R; the products of two fp32 values are exact in
 // fp64, the sum runs over the column's entries in ascending k.
 template <bool LDS>
@@ -252,28 +242,13 @@ __global__ __launch_bounds__(kBlock) void k_knn_rank(const int64_t *__restrict__
     const int64_t u = users[b];
     const bool valid = u >= 0 && u < n_rows;
     const int64_t beg = valid ? l_ptr[u] : 0, end = valid ? l_ptr[u + 1] : 0;
-    if (LDS) {
-        for (int64_t i = threadIdx.x; i < inner; i += kBlock) knn_x[i] = 0.f;
-        __syncthreads();
-        for (int64_t e = beg + threadIdx.x; e < end; e += kBlock) {
-            const int32_t c = l_col[e];
-            if (c >= 0 && c < inner) knn_x[c] = l_val[e];
-        }
-        __syncthreads();
-    }
+    if (LDS) sparse_row_to_lds(knn_x, inner, l_col, l_val, beg, end);
     double *row = scores + b * C;
     for (int64_t c = threadIdx.x; c < C; c += kBlock) {
         const int64_t it = items ? items[b * C + c] : c;
         double s = 0.0;
-        if (valid && it >= 0 && it < n_cols) {
-            const int64_t pe = r_ptr[it + 1];
-            for (int64_t e = r_ptr[it]; e < pe; ++e) {
-                const int32_t k = r_row[e];
-                if (k < 0 || k >= inner) continue;
-                const float xv = LDS ? knn_x[k] : knn_lookup(l_col, l_val, beg, end, k);
-                s += (double)xv * (double)r_val[e];
-            }
-        }
+        if (valid && it >= 0 && it < n_cols)
+            s = sparse_dot_score<LDS>(knn_x, l_col, l_val, beg, end, inner, r_ptr, r_row, r_val, it);
         row[c] = s;
     }
     if (!out_ids) return;

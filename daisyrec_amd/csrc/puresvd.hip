@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "score_f64.h"
 #include "topk_f64.h"
 
 namespace daisy {
@@ -286,10 +287,7 @@ __global__ __launch_bounds__(kBlock) void k_psvd_rank(const double *__restrict__
     for (int64_t cidx = tid; cidx < C; cidx += kBlock) {
         const int64_t it = items ? items[b * C + cidx] : cidx;
         double s = 0.0;
-        if (valid && it >= 0 && it < I) {
-            const double *__restrict__ iv = item_vec + it * k;
-            for (int f = 0; f < k; ++f) s = fma(uv[f], iv[f], s);
-        }
+        if (valid && it >= 0 && it < I) s = psvd_score(uv, item_vec + it * k, k);
         row[cidx] = s;
     }
     if (!out_ids) return;

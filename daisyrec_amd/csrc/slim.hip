@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "gemm.h"
+#include "score_f64.h"
 
 namespace daisy {
 namespace {
@@ -259,17 +260,6 @@ __global__ __launch_bounds__(kBlock) void k_slim_cd(SlimCdArgs p) {
 }
 
 // ---- scores ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float slim_lookup(const int32_t *__restrict__ col, const float *__restrict__ val, int64_t beg,
-                                             int64_t end, int32_t r) {
-    while (beg < end) {                                 // columns ascend within a row
-        const int64_t mid = beg + (end - beg) / 2;
-        const int32_t c = col[mid];
-        if (c == r) return val[mid];
-        if (c < r) beg = mid + 1; else end = mid;
-    }
-    return 0.f;
-}
-
 template <bool LDS>
 __global__ __launch_bounds__(kBlock) void k_slim_scores(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
                                                         const float *__restrict__ val, int64_t U, int64_t I,
@@ -281,28 +271,12 @@ __global__ __launch_bounds__(kBlock) void k_slim_scores(const int64_t *__restric
     const int64_t u = users[b];
     const bool valid = u >= 0 && u < U;
     const int64_t beg = valid ? row_ptr[u] : 0, end = valid ? row_ptr[u + 1] : 0;
-    if (LDS) {
-        for (int64_t i = threadIdx.x; i < I; i += kBlock) slim_x[i] = 0.f;
-        __syncthreads();
-        for (int64_t e = beg + threadIdx.x; e < end; e += kBlock) {
-            const int32_t c = col[e];
-            if (c >= 0 && c < I) slim_x[c] = val[e];
-        }
-        __syncthreads();
-    }
+    if (LDS) sparse_row_to_lds(slim_x, I, col, val, beg, end);
     const int64_t width = items ? C : I;
     for (int64_t c = threadIdx.x; c < width; c += kBlock) {
         const int64_t it = items ? items[b * C + c] : c;
         double s = 0.0;
-        if (valid && it >= 0 && it < I) {
-            const int64_t pe = w_ptr[it + 1];
-            for (int64_t e = w_ptr[it]; e < pe; ++e) {             // ascending row: the order of the fp64 sum
-                const int32_t r = w_row[e];
-                if (r < 0 || r >= I) continue;
-                const float xv = LDS ? slim_x[r] : slim_lookup(col, val, beg, end, r);
-                s += (double)xv * (double)w_val[e];
-            }
-        }
+        if (valid && it >= 0 && it < I) s = sparse_dot_score<LDS>(slim_x, col, val, beg, end, I, w_ptr, w_row, w_val, it);
         out[b * width + c] = (float)s;
     }
 }

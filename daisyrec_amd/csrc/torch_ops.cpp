@@ -24,6 +24,9 @@
 //                                 act) -> scores                            daisy_nfm_scores (eval mode)  NFMRecommender.py:110-209
 //   torch.ops.daisyrec.vae_scores(W, row_ptr, col, val, users, items, hidden, latent_dim, item_num) -> scores
 //                                                                           daisy_vae_scores (eval mode)  VAECFRecommender.py:79-145
+//   torch.ops.daisyrec.{ease,slim,knn,psvd}_full_rank_users(model operands, users, excl_indptr, excl_items, topk) -> (ids, scores)
+//                                                                           daisy_{ease,slim,knn,psvd}_full_rank_users (no counterpart:
+//                                                                           full ranking of many users)
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -297,6 +300,108 @@ at::Tensor vae_scores(const at::Tensor &W, const at::Tensor &row_ptr, const at::
     return out;
 }
 
+// ---- full ranking of many users on fp64 scores -> (ids int64 [n, topk], scores [n, topk])
+struct ExclPtrs {
+    const int64_t *indptr = nullptr;
+    const int32_t *items = nullptr;
+};
+ExclPtrs exclusion_of(const c10::optional<at::Tensor> &indptr, const c10::optional<at::Tensor> &items, const at::Tensor &first,
+                      int64_t user_num, const char *op) {
+    ExclPtrs e;
+    const bool a = indptr.has_value() && indptr->defined(), b = items.has_value() && items->defined();
+    TORCH_CHECK(a == b, op, ": excl_indptr and excl_items are given together or not at all");
+    if (!a) return e;
+    need(*indptr, at::kLong, "excl_indptr"); need(*items, at::kInt, "excl_items");
+    same_device(first, {&*indptr, &*items}, op);
+    TORCH_CHECK(indptr->numel() == user_num + 1, op, ": excl_indptr has ", indptr->numel(), " entries, expected ", user_num + 1);
+    TORCH_CHECK(items->numel() >= 1, op, ": excl_items is empty (pass no exclusion instead)");
+    e.indptr = indptr->data_ptr<int64_t>();
+    e.items = items->data_ptr<int32_t>();
+    return e;
+}
+void csr_of(const at::Tensor &ptr, const at::Tensor &idx, const at::Tensor &val, const char *op) {
+    need(ptr, at::kLong, "ptr"); need(idx, at::kInt, "idx"); need(val, at::kFloat, "val");
+    TORCH_CHECK(ptr.dim() == 1 && ptr.numel() >= 2 && idx.numel() == val.numel() && idx.numel() >= 1, op, ": CSR shapes");
+}
+
+std::tuple<at::Tensor, at::Tensor> ease_full_rank_users(const at::Tensor &row_ptr, const at::Tensor &col, const at::Tensor &val,
+                                                        const at::Tensor &W, const at::Tensor &users,
+                                                        const c10::optional<at::Tensor> &excl_indptr,
+                                                        const c10::optional<at::Tensor> &excl_items, int64_t topk) {
+    const char *op = "ease_full_rank_users";
+    csr_of(row_ptr, col, val, op);
+    need(W, at::kDouble, "W"); need(users, at::kLong, "users");
+    TORCH_CHECK(W.dim() == 2 && W.size(0) == W.size(1), op, ": W must be square");
+    same_device(W, {&row_ptr, &col, &val, &users}, op);
+    const c10::OptionalDeviceGuard guard(W.device());
+    const int64_t U = row_ptr.numel() - 1, n = users.numel();
+    const ExclPtrs e = exclusion_of(excl_indptr, excl_items, W, U, op);
+    at::Tensor ids = at::empty({n, topk}, users.options()), scores = at::empty({n, topk}, W.options());
+    ok(daisy_ease_full_rank_users(row_ptr.data_ptr<int64_t>(), col.data_ptr<int32_t>(), val.data_ptr<float>(), W.data_ptr<double>(),
+                                  U, W.size(0), n ? users.data_ptr<int64_t>() : nullptr, n, e.indptr, e.items, (int32_t)topk,
+                                  n ? ids.data_ptr<int64_t>() : nullptr, n ? scores.data_ptr<double>() : nullptr, stream_of(W)));
+    return {ids, scores};
+}
+
+std::tuple<at::Tensor, at::Tensor> slim_full_rank_users(const at::Tensor &row_ptr, const at::Tensor &col, const at::Tensor &val,
+                                                        const at::Tensor &w_ptr, const at::Tensor &w_row, const at::Tensor &w_val,
+                                                        const at::Tensor &users, const c10::optional<at::Tensor> &excl_indptr,
+                                                        const c10::optional<at::Tensor> &excl_items, int64_t topk) {
+    const char *op = "slim_full_rank_users";
+    csr_of(row_ptr, col, val, op); csr_of(w_ptr, w_row, w_val, op);
+    need(users, at::kLong, "users");
+    same_device(val, {&row_ptr, &col, &w_ptr, &w_row, &w_val, &users}, op);
+    const c10::OptionalDeviceGuard guard(val.device());
+    const int64_t U = row_ptr.numel() - 1, I = w_ptr.numel() - 1, n = users.numel();
+    const ExclPtrs e = exclusion_of(excl_indptr, excl_items, val, U, op);
+    at::Tensor ids = at::empty({n, topk}, users.options()), scores = at::empty({n, topk}, val.options());
+    ok(daisy_slim_full_rank_users(row_ptr.data_ptr<int64_t>(), col.data_ptr<int32_t>(), val.data_ptr<float>(), U, I,
+                                  w_ptr.data_ptr<int64_t>(), w_row.data_ptr<int32_t>(), w_val.data_ptr<float>(),
+                                  n ? users.data_ptr<int64_t>() : nullptr, n, e.indptr, e.items, (int32_t)topk,
+                                  n ? ids.data_ptr<int64_t>() : nullptr, n ? scores.data_ptr<float>() : nullptr,
+                                  DAISY_SLIM_PATH_AUTO, stream_of(val)));
+    return {ids, scores};
+}
+
+std::tuple<at::Tensor, at::Tensor> knn_full_rank_users(const at::Tensor &l_ptr, const at::Tensor &l_col, const at::Tensor &l_val,
+                                                       int64_t inner, const at::Tensor &r_ptr, const at::Tensor &r_row,
+                                                       const at::Tensor &r_val, const at::Tensor &users,
+                                                       const c10::optional<at::Tensor> &excl_indptr,
+                                                       const c10::optional<at::Tensor> &excl_items, int64_t topk) {
+    const char *op = "knn_full_rank_users";
+    csr_of(l_ptr, l_col, l_val, op); csr_of(r_ptr, r_row, r_val, op);
+    need(users, at::kLong, "users");
+    same_device(l_val, {&l_ptr, &l_col, &r_ptr, &r_row, &r_val, &users}, op);
+    const c10::OptionalDeviceGuard guard(l_val.device());
+    const int64_t U = l_ptr.numel() - 1, I = r_ptr.numel() - 1, n = users.numel();
+    const ExclPtrs e = exclusion_of(excl_indptr, excl_items, l_val, U, op);
+    at::Tensor ids = at::empty({n, topk}, users.options()), scores = at::empty({n, topk}, l_val.options().dtype(at::kDouble));
+    ok(daisy_knn_full_rank_users(l_ptr.data_ptr<int64_t>(), l_col.data_ptr<int32_t>(), l_val.data_ptr<float>(), U, inner,
+                                 r_ptr.data_ptr<int64_t>(), r_row.data_ptr<int32_t>(), r_val.data_ptr<float>(), I,
+                                 n ? users.data_ptr<int64_t>() : nullptr, n, e.indptr, e.items, (int32_t)topk,
+                                 n ? ids.data_ptr<int64_t>() : nullptr, n ? scores.data_ptr<double>() : nullptr,
+                                 DAISY_SLIM_PATH_AUTO, stream_of(l_val)));
+    return {ids, scores};
+}
+
+std::tuple<at::Tensor, at::Tensor> psvd_full_rank_users(const at::Tensor &user_vec, const at::Tensor &item_vec,
+                                                        const at::Tensor &users, const c10::optional<at::Tensor> &excl_indptr,
+                                                        const c10::optional<at::Tensor> &excl_items, int64_t topk) {
+    const char *op = "psvd_full_rank_users";
+    need(user_vec, at::kDouble, "user_vec"); need(item_vec, at::kDouble, "item_vec"); need(users, at::kLong, "users");
+    TORCH_CHECK(user_vec.dim() == 2 && item_vec.dim() == 2 && user_vec.size(1) == item_vec.size(1), op, ": factor counts differ");
+    same_device(user_vec, {&item_vec, &users}, op);
+    const c10::OptionalDeviceGuard guard(user_vec.device());
+    const int64_t U = user_vec.size(0), n = users.numel();
+    const ExclPtrs e = exclusion_of(excl_indptr, excl_items, user_vec, U, op);
+    at::Tensor ids = at::empty({n, topk}, users.options()), scores = at::empty({n, topk}, user_vec.options());
+    ok(daisy_psvd_full_rank_users(user_vec.data_ptr<double>(), item_vec.data_ptr<double>(), U, item_vec.size(0),
+                                  (int32_t)user_vec.size(1), n ? users.data_ptr<int64_t>() : nullptr, n, e.indptr, e.items,
+                                  (int32_t)topk, n ? ids.data_ptr<int64_t>() : nullptr, n ? scores.data_ptr<double>() : nullptr,
+                                  stream_of(user_vec)));
+    return {ids, scores};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(daisyrec, m) {
@@ -315,6 +420,14 @@ TORCH_LIBRARY(daisyrec, m) {
           "int n, int act) -> Tensor");
     m.def("vae_scores(Tensor W, Tensor row_ptr, Tensor col, Tensor val, Tensor users, Tensor? items, int[] hidden, "
           "int latent_dim, int item_num) -> Tensor");
+    m.def("ease_full_rank_users(Tensor row_ptr, Tensor col, Tensor val, Tensor W, Tensor users, Tensor? excl_indptr, "
+          "Tensor? excl_items, int topk) -> (Tensor, Tensor)");
+    m.def("slim_full_rank_users(Tensor row_ptr, Tensor col, Tensor val, Tensor w_ptr, Tensor w_row, Tensor w_val, Tensor users, "
+          "Tensor? excl_indptr, Tensor? excl_items, int topk) -> (Tensor, Tensor)");
+    m.def("knn_full_rank_users(Tensor l_ptr, Tensor l_col, Tensor l_val, int inner, Tensor r_ptr, Tensor r_row, Tensor r_val, "
+          "Tensor users, Tensor? excl_indptr, Tensor? excl_items, int topk) -> (Tensor, Tensor)");
+    m.def("psvd_full_rank_users(Tensor user_vec, Tensor item_vec, Tensor users, Tensor? excl_indptr, Tensor? excl_items, "
+          "int topk) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP key of a ROCm build
@@ -327,4 +440,8 @@ TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP
     m.impl("ngcf_layer_bwd", &ngcf_layer_bwd);
     m.impl("nfm_scores", &nfm_scores);
     m.impl("vae_scores", &vae_scores);
+    m.impl("ease_full_rank_users", &ease_full_rank_users);
+    m.impl("slim_full_rank_users", &slim_full_rank_users);
+    m.impl("knn_full_rank_users", &knn_full_rank_users);
+    m.impl("psvd_full_rank_users", &psvd_full_rank_users);
 }

@@ -98,19 +98,27 @@ class AbstractRecommender(nn.Module):
 
     def full_rank_users(self, users, exclude=None, return_scores=False):
         """Full ranking of many users at once (no counterpart in the reference): the models that score by a dot
-        product of two fp32 tables implement it (MF, FM, LightGCN, NGCF, Item2Vec)."""
+        product of two fp32 tables implement it (MF, FM, LightGCN, NGCF, Item2Vec), and so do the models
+        whose score is a fixed-order fp64 sum (EASE, SLiM, ItemKNNCF, UserKNNCF, PureSVD)."""
         raise NotImplementedError(f"{type(self).__name__} has no full_rank_users: it does not score by a dot product of "
                                   "two embedding tables")
 
     def _full_rank_users(self, P, Q, users, exclude, return_scores, biases=None):
         """full_rank_users of a dot-product model over its tables: `exclude` is None, an (indptr, items) device CSR
         (utils.user_csr) or a train_ur dict of sets, converted like build_candidates_set converts it."""
+        users, exclude = self._users_and_exclusion(users, exclude, int(P.shape[0]), P.device)
+        return ops.full_rank_users(P, Q, users, self.topk, exclude=exclude, biases=biases, return_scores=return_scores)
+
+    @staticmethod
+    def _users_and_exclusion(users, exclude, user_num, device):
+        """(users as a tensor, exclude as None or a device CSR): a train_ur dict of sets is converted like
+        build_candidates_set converts it"""
         if isinstance(exclude, dict):
             from ..utils.utils import _ur_pairs, user_csr
-            exclude = user_csr(_ur_pairs(exclude), int(P.shape[0]), P.device)
+            exclude = user_csr(_ur_pairs(exclude), int(user_num), device)
         if not isinstance(users, torch.Tensor):
             users = torch.as_tensor(np.asarray(users, dtype=np.int64))
-        return ops.full_rank_users(P, Q, users, self.topk, exclude=exclude, biases=biases, return_scores=return_scores)
+        return users, exclude
 
     def _resolve_optimizer(self, name=None):
         """AbstractRecommender.py:48-67: unknown names fall back to Adam with a log line.  'sparse_adam'

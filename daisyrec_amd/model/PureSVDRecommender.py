@@ -147,3 +147,13 @@ class PureSVD(GeneralRecommender):
     def full_rank(self, u):
         """PureSVDRecommender.py:80-83 -> int64 [topk] over all items."""
         return self._rank([int(u)], None, self.topk)[1].view(-1).cpu().numpy()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False):
+        """Full ranking of many users in one launch (no counterpart in the reference): device int64
+        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
+        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
+        return_scores: (ids, float64 scores)."""
+        self._fitted()
+        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
+        return ops.psvd_full_rank_users(self._user_vec, self._item_vec, users, self.topk, exclude=exclude,
+                                        return_scores=return_scores)

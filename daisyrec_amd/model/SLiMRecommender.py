@@ -138,6 +138,16 @@ class SLiM(GeneralRecommender):
         scores = self._scores([int(u)])
         return ops.full_topk_from_scores(scores.view(-1), min(self.topk, self.item_num)).cpu().numpy()
 
+    def full_rank_users(self, users, exclude=None, return_scores=False):
+        """Full ranking of many users in one launch (no counterpart in the reference): device int64
+        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
+        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
+        return_scores: (ids, float32 scores)."""
+        self._fitted()
+        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
+        return ops.slim_full_rank_users(self._csr, self._W, self.item_num, users, self.topk, exclude=exclude,
+                                        return_scores=return_scores)
+
     # -- the reference's attributes, built on demand -------------------------------------------------------------------
     @property
     def w_sparse(self):

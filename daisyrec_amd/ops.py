@@ -1898,6 +1898,98 @@ def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
     return scores, ids
 
 
+# ---- full ranking of many users on fp64 scores (csrc/rank_full_f64.hip) ------------------------------------
+RANK_F64_TOPK_CAP = 128       # kRfTopkCap (csrc/rank_f64_users.h): the candidate buffer of a user lives in LDS
+
+
+def _rank_f64_users_args(users, user_num, topk, exclude, return_scores, validate, device, score_dtype):
+    """What the four *_full_rank_users share: (users int64 [n], n, topk, exclusion pointers, ids [n, topk], scores or None).
+    validate: IndexError for a user id outside [0, user_num), ValueError for an exclusion that is not a CSR with ascending
+    rows (ops.full_rank_users' checks, one read-back each)."""
+    users = torch.as_tensor(users).to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+    n, topk = users.numel(), int(topk)
+    if topk > RANK_F64_TOPK_CAP:
+        raise ValueError(f"topk={topk} above the cap of {RANK_F64_TOPK_CAP} (the candidate buffer lives in LDS)")
+    if topk < 1:
+        raise ValueError(f"topk={topk} must be >= 1")
+    indptr = items = None
+    if exclude is not None:
+        indptr, items = exclude
+        if items.numel() == 0:              # (an empty tensor has no pointer to hand over)
+            items = torch.zeros(1, dtype=torch.int32, device=device)
+    if n and validate:
+        lo, hi = (int(x) for x in torch.stack([users.min(), users.max()]).tolist())
+        if lo < 0 or hi >= user_num:
+            raise IndexError(f"index {hi if hi >= user_num else lo} is out of bounds for the user table with {user_num} rows")
+        if exclude is not None:
+            _check_exclusion(indptr, exclude[1], user_num)
+    ids = torch.empty(n, topk, dtype=torch.int64, device=device)
+    scores = torch.empty(n, topk, dtype=score_dtype, device=device) if return_scores else None
+    excl = (_ptr(indptr, torch.int64, "exclude indptr"), _ptr(items, torch.int32, "exclude items"))
+    return users, n, topk, excl, ids, scores, (indptr, items)
+
+
+def ease_full_rank_users(csr, W, users, topk, exclude=None, return_scores=False, validate=True):
+    """Full ranking of many users by EASE's scores X[users] W in one launch (daisy_ease_full_rank_users):
+    int64 [n, topk] device ids of the best items of ALL I, best first by the float64 score of ease_rank (the same bits),
+    equal scores by ascending id, NaN never selected, without the items of the user's row of `exclude` = (indptr int64
+    [U + 1], items int32 ascending per row).  Positions beyond a user's eligible items hold -1 (score -inf); topk above I
+    is allowed, above RANK_F64_TOPK_CAP a ValueError.  return_scores: (ids, float64 scores).  validate: as
+    ops.full_rank_users.  No [n, I] array is written."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    wp, I = _ease_square(W, "W")
+    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate, W.device,
+                                                                    torch.float64)
+    check(lib.daisy_ease_full_rank_users(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
+                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"), _stream()))
+    return (ids, scores) if return_scores else ids
+
+
+def slim_full_rank_users(csr, W, item_num, users, topk, exclude=None, return_scores=False, validate=True, path="auto"):
+    """ease_full_rank_users for SLiM (daisy_slim_full_rank_users): the ranking is on slim_scores' float32 values (the
+    float64 sum rounded once), returned as float32.  W: slim_columns' triple; path as slim_scores."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    w_ptr, w_row, w_val = W
+    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate,
+                                                                    w_ptr.device, torch.float32)
+    check(lib.daisy_slim_full_rank_users(rp, cp, vp, U, int(item_num), _ptr(w_ptr, torch.int64, "w_ptr"),
+                                         _ptr(w_row, torch.int32, "w_row"), _ptr(w_val, torch.float32, "w_val"),
+                                         _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
+                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float32, "scores"),
+                                         N.SLIM_PATHS[path], _stream()))
+    return (ids, scores) if return_scores else ids
+
+
+def knn_full_rank_users(L, R, inner, n_cols, users, topk, exclude=None, return_scores=False, validate=True, path="auto"):
+    """ease_full_rank_users for ItemKNN / UserKNN (daisy_knn_full_rank_users): the float64 scores L[users] R of knn_rank.
+    L: a CSR triple [U, inner]; R: a by-column triple [inner, n_cols]; path as knn_rank."""
+    lp, lc, lv, n_rows = _slim_csr_ptrs(L)
+    rp, rc, rv, nc = _slim_csr_ptrs(R)
+    if nc != int(n_cols):
+        raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
+    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, n_rows, topk, exclude, return_scores, validate,
+                                                                    L[0].device, torch.float64)
+    check(lib.daisy_knn_full_rank_users(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols),
+                                        _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
+                                        _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"),
+                                        N.SLIM_PATHS[path], _stream()))
+    return (ids, scores) if return_scores else ids
+
+
+def psvd_full_rank_users(user_vec, item_vec, users, topk, exclude=None, return_scores=False, validate=True):
+    """ease_full_rank_users for PureSVD (daisy_psvd_full_rank_users): the float64 scores <user_vec[u], item_vec[i]> of
+    psvd_rank."""
+    up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
+    U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
+    if item_vec.shape[1] != k:
+        raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
+    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate,
+                                                                    user_vec.device, torch.float64)
+    check(lib.daisy_psvd_full_rank_users(up, ip, U, I, k, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
+                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"), _stream()))
+    return (ids, scores) if return_scores else ids
+
+
 # ---- MostPop and the ranking KPIs (csrc/pop.hip, csrc/metrics.hip; DESIGN.md §20) ----------------------------------------
 def _ids_ptr(t, name):
     """(pointer, is_i64) of a contiguous int32 / int64 device tensor of ids"""

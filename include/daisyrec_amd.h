@@ -1125,6 +1125,41 @@ size_t daisy_knn_fit_bytes(int64_t n_rows, int64_t n, int32_t K);
 int daisy_knn_fits(int64_t n_rows, int64_t n, int32_t K, size_t offered_bytes);
 
 /* ------------------------------------------------------------------------
+ * Full ranking of many users on fp64 scores: EASE, SLiM, ItemKNN / UserKNN, PureSVD (csrc/rank_full_f64.hip,
+ * csrc/rank_f64_users.h, csrc/score_f64.h; additive to ABI 8)
+ * ---------------------------------------------------------------------- */
+/* For every users[b] (int64 [n], any order, duplicates allowed) the topk items of ALL item_num (n_cols), best first, without
+ * the items of the user's exclusion row, in one launch of one workgroup per user.  The score of (user, item) is the
+ * model's own: the expression of daisy_ease_rank, daisy_slim_scores, daisy_knn_rank and daisy_psvd_rank, from the same
+ * device function, so the bits agree; the model arguments are those entries' without items / C / scores.  Order: score
+ * descending compared as fp64 (SLiM: after its rounding to fp32), -0.0 equal to +0.0, equal scores by ascending item id,
+ * a score that is not a number is never selected.  The exclusion is daisy_full_rank_users': excl_indptr int64
+ * [user_num + 1] (n_rows for knn), excl_items int32 ascending inside a row, duplicates allowed, both NULL or both given;
+ * row contents are only compared, never used as an index: an entry >= item_num or an unsorted row may cost missed
+ * exclusions, never an out-of-bounds access; user ids and excl_indptr are the caller's to validate (a user id out of range
+ * scores 0 everywhere and excludes nothing).  out_ids int64 [n, topk]; out_scores [n, topk] (fp64; fp32 for SLiM) or
+ * NULL; positions beyond a user's eligible, comparable items hold id -1 and score -inf.  1 <= topk <= 128 (topk above
+ * item_num is allowed): a larger topk is DAISY_ERR_ARG with the cap in the message.  Every argument is checked before the
+ * first HIP call; n == 0 returns DAISY_OK without a launch.  No workspace: daisy_rank_f64_users_workspace_bytes is 0 for
+ * every shape - the candidates of a user live in LDS and nothing of size n * item_num is written or allocated. */
+size_t daisy_rank_f64_users_workspace_bytes(int64_t n, int64_t item_num, int32_t topk);
+int daisy_ease_full_rank_users(const int64_t *row_ptr, const int32_t *col, const float *val, const double *W, int64_t user_num,
+                               int64_t item_num, const int64_t *users, int64_t n, const int64_t *excl_indptr,
+                               const int32_t *excl_items, int32_t topk, int64_t *out_ids, double *out_scores,
+                               daisy_stream_t stream);
+int daisy_slim_full_rank_users(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t user_num, int64_t item_num,
+                               const int64_t *w_ptr, const int32_t *w_row, const float *w_val, const int64_t *users, int64_t n,
+                               const int64_t *excl_indptr, const int32_t *excl_items, int32_t topk, int64_t *out_ids,
+                               float *out_scores, int32_t path, daisy_stream_t stream);
+int daisy_knn_full_rank_users(const int64_t *l_ptr, const int32_t *l_col, const float *l_val, int64_t n_rows, int64_t inner,
+                              const int64_t *r_ptr, const int32_t *r_row, const float *r_val, int64_t n_cols,
+                              const int64_t *users, int64_t n, const int64_t *excl_indptr, const int32_t *excl_items,
+                              int32_t topk, int64_t *out_ids, double *out_scores, int32_t path, daisy_stream_t stream);
+int daisy_psvd_full_rank_users(const double *user_vec, const double *item_vec, int64_t user_num, int64_t item_num, int32_t k,
+                               const int64_t *users, int64_t n, const int64_t *excl_indptr, const int32_t *excl_items,
+                               int32_t topk, int64_t *out_ids, double *out_scores, daisy_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * MostPop (daisy/model/PopRecommender.py) and the ranking KPIs (daisy/utils/metrics.py): csrc/pop.hip, csrc/metrics.hip;
  * DESIGN.md §20.
  * ---------------------------------------------------------------------- */
