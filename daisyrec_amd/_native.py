@@ -192,7 +192,8 @@ SIGNATURES = {
     "daisy_neumf_ctx_bytes": (_sz, [_p]),
     "daisy_neumf_ctx_set_precision": (C.c_int, [_p, _i32]),
     "daisy_neumf_scores": (C.c_int, [_p, _pp, _p, _p, _i64, _i64, _p, _p]),
-    "daisy_neumf_step_grads": (C.c_int, [_p, _pp, _pp, _p, _p, _p, _i64, _i32, _f32, _f32, _f32, _f32, _u64, _p, _p]),
+    "daisy_neumf_scores_users": (C.c_int, [_p, _pp, _p, _i64, _p, _p]),
+    "daisy_neumf_step_grads":(C.c_int, [_p, _pp, _pp, _p, _p, _p, _i64, _i32, _f32, _f32, _f32, _f32, _u64, _p, _p]),
     "daisy_neumf_fit_epoch": (C.c_int, [_p, _pp, _pp, _p, _p, _p, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _u64, _i64,
                                         _i32, _f32, _p, _p, _p, _p, _i64, _p, _p]),
     "daisy_sgd_dense": (C.c_int, [_p, _p, _i64, _f32, _p]),
@@ -226,7 +227,8 @@ SIGNATURES = {
     "daisy_nfm_fit_epoch": (C.c_int, [_p, _np, _np, _nb, _p, _p, _p, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _u64,
                                       _i64, _i64, _i32, _f32, _p, _p, _p, _p, _i64, _p, _p]),
     "daisy_nfm_scores": (C.c_int, [_p, _np, _nb, _p, _p, _i64, _i64, _i32, _f32, _u64, _p, _p]),
-    "daisy_vae_ctx_create": (C.c_int, [C.POINTER(_p), _i64, _i64, _i64, _i32, _p, _i32]),
+    "daisy_nfm_scores_users": (C.c_int, [_p, _np, _nb, _p, _i64, _p, _p]),
+    "daisy_vae_ctx_create":(C.c_int, [C.POINTER(_p), _i64, _i64, _i64, _i32, _p, _i32]),
     "daisy_vae_ctx_destroy": (C.c_int, [_p]),
     "daisy_vae_ctx_bytes": (_sz, [_p]),
     "daisy_vae_param_count": (_i64, [_p]),
@@ -272,7 +274,8 @@ SIGNATURES = {
     "daisy_knn_full_rank_users": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _i32, _p, _p, _i32,
                                             _p]),
     "daisy_psvd_full_rank_users": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p, _i32, _p, _p, _p]),
-    "daisy_pop_fit": (C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
+    "daisy_rank_rows_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p]),
+    "daisy_pop_fit":(C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
     "daisy_pop_rank": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
     "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),
     "daisy_ranking_kpis": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _i64, _p, _i32,

@@ -994,6 +994,25 @@ int daisy_neumf_scores(daisy_neumf_ctx *ctx, const daisy_neumf_params *params, c
     return DAISY_OK;
 }
 
+int daisy_neumf_scores_users(daisy_neumf_ctx *ctx, const daisy_neumf_params *params, const int64_t *users, int64_t m,
+                             float *out, daisy_stream_t stream) {
+    DAISY_CHECK_ARG(ctx && params && users && out && m > 0, "neumf_scores_users: bad argument");
+    DAISY_CHECK_ARG(m <= INT64_MAX / ctx->I, "neumf_scores_users: m=%lld users x %lld items overflow", (long long)m,
+                    (long long)ctx->I);
+    hipStream_t s = as_stream(stream);
+    const int64_t n = m * ctx->I;
+    for (int64_t base = 0; base < n; base += ctx->max_rows) {
+        const int64_t R = (n - base < ctx->max_rows) ? (n - base) : ctx->max_rows;
+        PairSrc src{};
+        src.users = users; src.all_items = ctx->I; src.base = base;
+        const NeumfPath path = neumf_path(ctx, *params, R, false, 0u);
+        int rc = neumf_forward_rows(ctx, params, path, src, R, false, 0, 0u, 1.f, 0, nullptr, nullptr, s);
+        if (rc) return rc;
+        DAISY_HIP(hipMemcpyAsync(out + base, ctx->pred, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return DAISY_OK;
+}
+
 int daisy_neumf_step_grads(daisy_neumf_ctx *ctx, const daisy_neumf_params *params,
                            const daisy_neumf_params *grads, const int32_t *u, const int32_t *i,
                            const int32_t *j, int64_t B, int32_t loss_type, float gamma, float reg_1,

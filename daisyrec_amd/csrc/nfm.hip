@@ -824,6 +824,35 @@ int nf_check_bn(const daisy_nfm_ctx *c, const daisy_nfm_bn_state *bn, const char
     return DAISY_OK;
 }
 
+// the eval-mode launch daisy_nfm_scores and daisy_nfm_scores_users share
+int nf_scores_eval(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_bn_state *bn, const PairSrc &src,
+                          int64_t n, float *out, hipStream_t s) {
+    NfEval a{};
+    a.P = params->P;
+    a.Q = params->Q;
+    a.ub = params->ub;
+    a.ib = params->ib;
+    a.bias = params->bias;
+    a.wp = params->wp;
+    for (int l = 0; l < ctx->L; ++l) {
+        a.W[l] = params->W[l];
+        a.b[l] = params->b[l];
+    }
+    for (int k = 0; k <= ctx->L; ++k)
+        if (ctx->bn) {
+            a.gamma[k] = params->bn_w[k];
+            a.beta[k] = params->bn_b[k];
+            a.rmean[k] = bn->mean[k];
+            a.rvar[k] = bn->var[k];
+        }
+    a.L = ctx->L;
+    a.d = ctx->d;
+    a.act = ctx->act;
+    hipLaunchKernelGGL(k_nfm_scores, dim3(grid_for((n + kNfTR - 1) / kNfTR, 1, 4096)), dim3(kBlock), 0, s, a, src, n, out);
+    DAISY_LAUNCH_CHECK();
+    return DAISY_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1078,30 +1107,20 @@ int daisy_nfm_scores(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const d
         DAISY_LAUNCH_CHECK();
         return DAISY_OK;
     }
-    NfEval a{};
-    a.P = params->P;
-    a.Q = params->Q;
-    a.ub = params->ub;
-    a.ib = params->ib;
-    a.bias = params->bias;
-    a.wp = params->wp;
-    for (int l = 0; l < ctx->L; ++l) {
-        a.W[l] = params->W[l];
-        a.b[l] = params->b[l];
-    }
-    for (int k = 0; k <= ctx->L; ++k)
-        if (ctx->bn) {
-            a.gamma[k] = params->bn_w[k];
-            a.beta[k] = params->bn_b[k];
-            a.rmean[k] = bn->mean[k];
-            a.rvar[k] = bn->var[k];
-        }
-    a.L = ctx->L;
-    a.d = ctx->d;
-    a.act = ctx->act;
-    hipLaunchKernelGGL(k_nfm_scores, dim3(grid_for((n + kNfTR - 1) / kNfTR, 1, 4096)), dim3(kBlock), 0, s, a, src, n, out);
-    DAISY_LAUNCH_CHECK();
-    return DAISY_OK;
+    return nf_scores_eval(ctx, params, bn, src, n, out, s);
+}
+
+int daisy_nfm_scores_users(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_bn_state *bn,
+                           const int64_t *users, int64_t m, float *out, daisy_stream_t stream) {
+    DAISY_CHECK_ARG(ctx && params && users && out, "nfm_scores_users: null argument");
+    DAISY_CHECK_ARG(m >= 1 && m <= INT64_MAX / ctx->item_num, "nfm_scores_users: m=%lld users (x %lld items)", (long long)m,
+                    (long long)ctx->item_num);
+    if (int rc = nf_check_params(ctx, params, "nfm_scores_users")) return rc;
+    if (int rc = nf_check_bn(ctx, bn, "nfm_scores_users", false)) return rc;
+    PairSrc src{};
+    src.users = users;
+    src.all_items = ctx->item_num;
+    return nf_scores_eval(ctx, params, bn, src, m * ctx->item_num, out, as_stream(stream));
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // not depend on append order, wave scheduling or the slice count.
 #include "common.h"
 #include "mfma.h"
+#include "rank_key_f32.h"                       // fr_key / fr_unkey: the score half of the sort word
 
 namespace daisy {
 
@@ -66,19 +67,6 @@ __device__ __forceinline__ void fr_sort_desc(uint64_t (&w)[4], int lane) {
             }
         }
     }
-}
-
-// order-preserving key of a score: larger score <-> larger key; NaN is the largest (torch.argsort(descending=True)
-// puts it first); v + 0.0f makes -0.0 and +0.0 one key
-__device__ __forceinline__ uint32_t fr_key(float v) {
-    v = v + 0.0f;
-    if (v != v) return 0xFFFFFFFFu;
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fr_unkey(uint32_t key) {
-    if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
 
 // One wave: the candidate words of user slot `u` (count c <= kFrBuf) sorted; the topk largest go back to the head of

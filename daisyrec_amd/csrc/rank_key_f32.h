@@ -1,0 +1,24 @@
+// The order-preserving 32-bit key of an fp32 score, shared by the full rankings on fp32 scores (rank_full.hip, DESIGN.md
+// section 24; rank_rows.hip, section 26).  Their 64-bit sort word is (fr_key(v) << 32) | (0xFFFFFFFF - item): a plain
+// unsigned maximum is then the order (score descending, a NaN first, -0.0 equal to +0.0, equal scores by ascending item
+// id), and no candidate maps to word 0.
+#pragma once
+
+#include "common.h"
+
+namespace daisy {
+
+// order-preserving key of a score: larger score <-> larger key; NaN is the largest (torch.argsort(descending=True)
+// puts it first); v + 0.0f makes -0.0 and +0.0 one key
+__device__ __forceinline__ uint32_t fr_key(float v) {
+    v = v + 0.0f;
+    if (v != v) return 0xFFFFFFFFu;
+    const uint32_t b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float fr_unkey(uint32_t key) {
+    if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+}  // namespace daisy

@@ -402,6 +402,39 @@ std::tuple<at::Tensor, at::Tensor> psvd_full_rank_users(const at::Tensor &user_v
     return {ids, scores};
 }
 
+// ---- masked top-k over rows of fp32 scores -> (ids int64 [m, topk], scores fp32 [m, topk]); scores'
+// rows are contiguous, its stride is the pitch
+std::tuple<at::Tensor, at::Tensor> rank_rows_f32(const at::Tensor &scores, const c10::optional<at::Tensor> &row_users,
+                                                 const c10::optional<at::Tensor> &excl_indptr,
+                                                 const c10::optional<at::Tensor> &excl_items, int64_t topk) {
+    const char *op = "rank_rows_f32";
+    TORCH_CHECK(scores.is_cuda(), "scores: expected a HIP device tensor (there is no CPU fallback)");
+    TORCH_CHECK(scores.scalar_type() == at::kFloat && scores.dim() == 2, op, ": scores must be a 2-D float32 tensor");
+    const int64_t m = scores.size(0), I = scores.size(1);
+    TORCH_CHECK(I >= 1 && (I == 1 || scores.stride(1) == 1) && (m <= 1 || scores.stride(0) >= I), op,
+                ": the rows of scores must be contiguous and must not overlap");
+    const c10::OptionalDeviceGuard guard(scores.device());
+    const int64_t *ru = nullptr;
+    ExclPtrs e;
+    if (excl_indptr.has_value() && excl_indptr->defined()) {
+        TORCH_CHECK(row_users.has_value() && row_users->defined(), op, ": an exclusion needs row_users");
+        e = exclusion_of(excl_indptr, excl_items, scores, excl_indptr->numel() - 1, op);
+    } else {
+        e = exclusion_of(excl_indptr, excl_items, scores, 0, op);
+    }
+    if (row_users.has_value() && row_users->defined()) {
+        need(*row_users, at::kLong, "row_users");
+        same_device(scores, {&*row_users}, op);
+        TORCH_CHECK(row_users->numel() == m, op, ": row_users has ", row_users->numel(), " entries for ", m, " rows");
+        if (m && e.indptr) ru = row_users->data_ptr<int64_t>();
+    }
+    const int64_t pitch = m > 1 ? scores.stride(0) : I;
+    at::Tensor ids = at::empty({m, topk}, scores.options().dtype(at::kLong)), out = at::empty({m, topk}, scores.options());
+    ok(daisy_rank_rows_f32(m ? scores.data_ptr<float>() : nullptr, m, I, pitch, ru, e.indptr, e.items, (int32_t)topk,
+                           m ? ids.data_ptr<int64_t>() : nullptr, m ? out.data_ptr<float>() : nullptr, stream_of(scores)));
+    return {ids, out};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(daisyrec, m) {
@@ -428,6 +461,8 @@ TORCH_LIBRARY(daisyrec, m) {
           "Tensor users, Tensor? excl_indptr, Tensor? excl_items, int topk) -> (Tensor, Tensor)");
     m.def("psvd_full_rank_users(Tensor user_vec, Tensor item_vec, Tensor users, Tensor? excl_indptr, Tensor? excl_items, "
           "int topk) -> (Tensor, Tensor)");
+    m.def("rank_rows_f32(Tensor scores, Tensor? row_users, Tensor? excl_indptr, Tensor? excl_items, int topk) -> "
+          "(Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP key of a ROCm build
@@ -444,4 +479,5 @@ TORCH_LIBRARY_IMPL(daisyrec, CUDA, m) {      // the CUDA dispatch key is the HIP
     m.impl("slim_full_rank_users", &slim_full_rank_users);
     m.impl("knn_full_rank_users", &knn_full_rank_users);
     m.impl("psvd_full_rank_users", &psvd_full_rank_users);
+    m.impl("rank_rows_f32", &rank_rows_f32);
 }

@@ -99,9 +99,51 @@ class AbstractRecommender(nn.Module):
     def full_rank_users(self, users, exclude=None, return_scores=False):
         """Full ranking of many users at once (no counterpart in the reference): the models that score by a dot
         product of two fp32 tables implement it (MF, FM, LightGCN, NGCF, Item2Vec), and so do the models
-        whose score is a fixed-order fp64 sum (EASE, SLiM, ItemKNNCF, UserKNNCF, PureSVD)."""
-        raise NotImplementedError(f"{type(self).__name__} has no full_rank_users: it does not score by a dot product of "
-                                  "two embedding tables")
+        whose score is a fixed-order fp64 sum (EASE, SLiM, ItemKNNCF, UserKNNCF, PureSVD) and the models
+        whose scores come out of a kernel of their own (NeuMF, NFM, VAECF)."""
+        raise NotImplementedError(f"{type(self).__name__} has no full_rank_users: the thirteen models that implement it "
+                                  "are listed in DESIGN.md §24-§26")
+
+    # the score chunk of _full_rank_users_scored: the best of the 16 / 64 / 256 MiB measured (DESIGN.md §26) - a score call has
+    # a fixed cost that larger chunks spread over more users (Multi-VAE's first encoder layer above all)
+    SCORED_CHUNK_BYTES = 256 << 20
+
+    def _full_rank_users_scored(self, users, exclude, return_scores, chunk_bytes, user_num, item_num, device, make_scorer,
+                                validate=True):
+        """full_rank_users of a model whose scores come out of a kernel of its own: per chunk of
+        rows = max(1, chunk_bytes // (4 I)) users one score call into a reused [rows, I] float32 buffer and one
+        ops.rank_rows_f32 into the chunk's slice of the outputs; nothing of size n * I is allocated and nothing is read
+        back between chunks.  make_scorer(users int64 [n] on the device, rows) is called once, after the checks, and returns
+        score(us, b0, b1, out): the scores of us = users[b0:b1] against all items into out [b1 - b0, I].  validate=False skips
+        the two read-backs of ops.full_rank_users' checks (the user ids and the exclusion are then trusted)."""
+        users, exclude = self._users_and_exclusion(users, exclude, user_num, device)
+        users = users.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+        n, I, topk = users.numel(), int(item_num), int(self.topk)
+        if topk > ops.RANK_ROWS_TOPK_CAP:
+            raise ValueError(f"topk={topk} above the cap of {ops.RANK_ROWS_TOPK_CAP} (the candidate buffer lives in LDS)")
+        if topk < 1:
+            raise ValueError(f"topk={topk} must be >= 1")
+        topk = min(topk, I)
+        if n and validate:                          # ops.full_rank_users' checks, once for all chunks
+            lo, hi = (int(x) for x in torch.stack([users.min(), users.max()]).tolist())
+            if lo < 0 or hi >= user_num:
+                raise IndexError(f"index {hi if hi >= user_num else lo} is out of bounds for the user table with {user_num} rows")
+            if exclude is not None:
+                ops._check_exclusion(exclude[0], exclude[1], int(user_num))
+        ids = torch.empty(n, topk, dtype=torch.int64, device=device)
+        scores = torch.empty(n, topk, dtype=torch.float32, device=device) if return_scores else None
+        if n:
+            nbytes = self.SCORED_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+            rows = min(n, max(1, nbytes // (4 * I)))
+            score = make_scorer(users, rows)
+            buf = torch.empty(rows, I, dtype=torch.float32, device=device)
+            for b0 in range(0, n, rows):
+                b1 = min(n, b0 + rows)
+                us, chunk = users[b0:b1], buf[:b1 - b0]
+                score(us, b0, b1, chunk)
+                ops.rank_rows_f32(chunk, topk, row_users=us, exclude=exclude, validate=False,
+                                  out=(ids[b0:b1], None if scores is None else scores[b0:b1]))
+        return (ids, scores) if return_scores else ids
 
     def _full_rank_users(self, P, Q, users, exclude, return_scores, biases=None):
         """full_rank_users of a dot-product model over its tables: `exclude` is None, an (indptr, items) device CSR

@@ -283,3 +283,25 @@ class NFM(GeneralRecommender):
         self._check_ids(users, None)
         scores = self._scores(users, None, C_=0, n=I)
         return ops.full_topk_from_scores(scores, self.topk).cpu().numpy()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False, chunk_bytes=None, validate=True):
+        """Full ranking of many users (no counterpart in the reference): device int64 [len(users),
+        min(topk, I)], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an (indptr,
+        items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.  return_scores:
+        (ids, float32 scores).  Eval mode only - batch statistics and dropout over an arbitrary chunk are not a ranking:
+        call model.eval() first.  chunk_bytes (default 256 MiB) of scores at a time through daisy_nfm_scores_users, then
+        ops.rank_rows_f32; the eval kernel computes a pair's score from the pair alone, so the result does not depend
+        on chunk_bytes, bit for bit.  Nothing of the model changes: not the running statistics, not the score-call count."""
+        if self.training:
+            raise RuntimeError("NFM.full_rank_users ranks in eval mode only (running statistics, no dropout): call "
+                               "model.eval() first")
+        p = self._params()
+        bn = self._bn()
+        ctx = self._score_ctx(1)
+        U, I = self.embed_user.num_embeddings, self.embed_item.num_embeddings
+
+        def make_scorer(us_all, rows):
+            return lambda us, b0, b1, out: ctx.scores_users(p, bn, us, out)
+
+        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, I, self.device, make_scorer,
+                                            validate=validate)         # (validate: as in ops.full_rank_users)

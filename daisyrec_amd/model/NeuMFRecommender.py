@@ -219,3 +219,27 @@ class NeuMF(GeneralRecommender):
             return ops.full_topk_from_scores(scores, self.topk).cpu().numpy()
         finally:
             ctx.close()
+
+    def full_rank_users(self, users, exclude=None, return_scores=False, chunk_bytes=None, validate=True):
+        """Full ranking of many users (no counterpart in the reference): device int64 [len(users),
+        min(topk, I)], best first, without the items of the user's row of `exclude` (None, an (indptr, items) device CSR
+        or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.  return_scores: (ids, float32
+        scores).  Scored in eval mode, as `forward` does, chunk_bytes (default 256 MiB) of scores at a time through
+        daisy_neumf_scores_users, then ops.rank_rows_f32: nothing of size n * I is allocated.  precision 'fp32': row b =
+        full_rank(users[b]) without its training items, whatever chunk_bytes is.  The bf16 precisions: the bits of a score
+        depend on the row count of the call that computes it (whole 128-row tiles run at level 2), so the promise is per
+        chunk - the chunk's lists are the exact ranking of what the score entry returns for that chunk's users."""
+        p = self._params()
+        U, I = self.embed_user_GMF.num_embeddings, self.embed_item_GMF.num_embeddings
+        ctxs = []
+
+        def make_scorer(us_all, rows):
+            ctxs.append(self._ctx(min(rows * I, 1 << 18)))
+            return lambda us, b0, b1, out: ctxs[0].scores_users(p, us, out)
+
+        try:
+            return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, I, self.device, make_scorer,
+                                                validate=validate)     # (validate: as in ops.full_rank_users)
+        finally:
+            for ctx in ctxs:
+                ctx.close()

@@ -272,3 +272,31 @@ class VAECF(AERecommender):
         scores = self._scores(torch.tensor([int(u)]))
         return ops.full_topk_from_scores(scores.view(-1), self.topk).cpu().numpy()
 
+    def full_rank_users(self, users, exclude=None, return_scores=False, chunk_bytes=None, validate=True):
+        """Full ranking of many users (no counterpart in the reference): device int64 [len(users),
+        min(topk, I)], best first, without the items of the user's row of `exclude` (None, an (indptr, items) device CSR
+        or a train_ur dict of sets) - the protocol Multi-VAE is evaluated under; -1 where a user has fewer eligible items
+        than topk.  return_scores: (ids, float32 scores).  Eval mode only - dropout and the reparameterisation noise over
+        an arbitrary chunk are not a ranking: call model.eval() first.  chunk_bytes (default 256 MiB) of scores at a time
+        through daisy_vae_scores in the shared score context (config['history_csr'] works as for rank), then
+        ops.rank_rows_f32.  The GEMMs pick their split-K from the call's row count and the context's workspace, so the bits
+        of a score depend on the chunk: the promise is per chunk - the chunk's lists are the exact ranking of what
+        `_scores` returns for exactly that chunk's users in the same context.  Neither `update` nor the score-call count
+        changes."""
+        if self.training:
+            raise RuntimeError("VAECF.full_rank_users ranks in eval mode only (no dropout, no reparameterisation noise): "
+                               "call model.eval() first")
+        W = self._params()
+        csr, lens = self._csr()
+        U = int(self.user_num) if self.history_csr is not None else int(self.history_item_id.shape[0])
+
+        def make_scorer(us_all, rows):
+            # the chunks' entry counts from the host copy of the row lengths: one copy of the ids, nothing per chunk
+            ulens = lens[us_all.cpu()]
+            entries = [int(x.sum()) for x in torch.split(ulens, rows)]
+            ctx = self._score_ctx(rows, max(entries))
+            return lambda us, b0, b1, out: ctx.scores(W, csr, us, entries[b0 // rows], out=out)
+
+        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, self.item_num, self.device,
+                                            make_scorer, validate=validate)
+

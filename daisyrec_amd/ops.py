@@ -926,6 +926,14 @@ class NeumfContext(_Native):
                                      _ptr(out, torch.float32, "out"), _stream()))
         return out
 
+    def scores_users(self, params, users, out):
+        """The eval-mode scores of users [m] (int64 device) against ALL items into out float32 [m, item_num] (contiguous):
+        daisy_neumf_scores_users - the forward code of `scores`, no candidate array."""
+        tab = _neumf_table(params, self.L)
+        check(lib.daisy_neumf_scores_users(self._h, C.byref(tab), _ptr(users, torch.int64, "users"), int(users.numel()),
+                                           _ptr(out, torch.float32, "out"), _stream()))
+        return out
+
     def step_grads(self, params, grads, u, i, j, loss_type=N.LOSS_BPR, reg_1=0.0, reg_2=0.0, dropout=0.0,
                    seed=0, gamma=1e-10):
         """NeuMF.calc_loss + backward for one batch: accumulates into `grads`, loss in stats[NST_LOSS]."""
@@ -1259,6 +1267,14 @@ class NfmContext(_Native):
                                    int(seed) & (2 ** 64 - 1), _ptr(out, torch.float32, "out"), _stream()))
         return out
 
+    def scores_users(self, params, bn, users, out):
+        """The eval-mode scores of users [m] (int64 device) against ALL items into out float32 [m, item_num] (contiguous):
+        daisy_nfm_scores_users - the kernel of `scores`, no candidate array; the running statistics are only read."""
+        pt, bt = _nfm_table(params, self.L, self.bn), _nfm_bn(bn, self.L)
+        check(lib.daisy_nfm_scores_users(self._h, C.byref(pt), C.byref(bt), _ptr(users, torch.int64, "users"),
+                                         int(users.numel()), _ptr(out, torch.float32, "out"), _stream()))
+        return out
+
     def step_grads(self, params, grads, bn, u, i, j, loss_type=N.LOSS_BPR, reg_1=0.0, reg_2=0.0, dropout=0.0, seed=0,
                    gamma=1e-10):
         """NFM.calc_loss + backward for one batch: accumulates into `grads`, updates `bn`; loss in stats[NFST_LOSS]."""
@@ -1381,18 +1397,22 @@ class VaeContext(_Native):
         optim.t += steps
         return steps
 
-    def scores(self, W, csr, users, n_entries, items=None, train=False, dropout=0.0, seed=0, keep=None, eps=None):
-        """VAECF.forward's scores of users [B]: [B, item_num], or [B, C] for candidates items [B, C] (int64)."""
+    def scores(self, W, csr, users, n_entries, items=None, train=False, dropout=0.0, seed=0, keep=None, eps=None, out=None):
+        """VAECF.forward's scores of users [B]: [B, item_num], or [B, C] for candidates items [B, C] (int64).  out: a
+        contiguous float32 [B, item_num] (or [B, C]) tensor to write into instead of a new one."""
         rp, cp, vp, U = self._csr(csr)
         users = users.to(torch.int64).contiguous()
         B = users.numel()
         if items is not None:
             items = items.to(torch.int64).contiguous()
             Cn = items.shape[1]
-            out = torch.empty(B, Cn, dtype=torch.float32, device=self.device)
         else:
             Cn = 0
-            out = torch.empty(B, self.item_num, dtype=torch.float32, device=self.device)
+        shape = (B, Cn if items is not None else self.item_num)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape:
+            raise ValueError(f"out: expected {shape}, got {tuple(out.shape)}")
         check(lib.daisy_vae_scores(self._h, _ptr(W, torch.float32, "W"), rp, cp, vp, U, _ptr(users, torch.int64, "users"), B,
                                    int(n_entries), _ptr(items, torch.int64, "items"), int(Cn), _ptr(keep, torch.uint8, "keep"),
                                    _ptr(eps, torch.float32, "eps"), int(bool(train)), float(dropout),
@@ -1988,6 +2008,63 @@ def psvd_full_rank_users(user_vec, item_vec, users, topk, exclude=None, return_s
     check(lib.daisy_psvd_full_rank_users(up, ip, U, I, k, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
                                          _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"), _stream()))
     return (ids, scores) if return_scores else ids
+
+
+# ---- masked top-k over rows of fp32 scores (csrc/rank_rows.hip) --------------------------------------------
+RANK_ROWS_TOPK_CAP = 128      # kRrTopkCap (csrc/rank_rows.hip): the candidate buffer of a row lives in LDS
+RANK_ROWS_STEP = 1024         # kRrStep: items a workgroup takes per step (the tests' edge sizes)
+
+
+def rank_rows_f32(scores, topk, row_users=None, exclude=None, return_scores=False, validate=True, out=None):
+    """The best topk items of every row of a score matrix in one launch (daisy_rank_rows_f32): scores is a
+    2-D float32 device tensor with contiguous rows (its stride is the pitch: a column slice of a wider matrix is fine),
+    the result int64 [m, min(topk, I)] device ids, best first - score descending, a NaN first, -0.0 equal to +0.0, equal
+    scores by ascending id (ops.full_rank_users' order).  `exclude` = (indptr int64 [U + 1], items int32 ascending per
+    row), the device CSR of build_user_csr, drops the items of CSR row row_users[r] (int64 [m], any order, duplicates
+    allowed) from score row r; a row with fewer eligible items than topk gets -1 (score -inf) in the remaining positions.
+    return_scores: (ids, float32 scores), each score the row's own stored value (the same bits).  topk above
+    RANK_ROWS_TOPK_CAP raises ValueError.  validate: IndexError for a row_users entry outside [0, U), ValueError for an
+    exclusion that is not such a CSR (one read-back each); False skips both - the kernel then trusts row_users and
+    indptr, and only ever compares row contents.  out: (ids, scores or None) to write into instead of new tensors."""
+    topk = int(topk)
+    if topk > RANK_ROWS_TOPK_CAP:
+        raise ValueError(f"topk={topk} above the cap of {RANK_ROWS_TOPK_CAP} (the candidate buffer lives in LDS)")
+    if topk < 1:
+        raise ValueError(f"topk={topk} must be >= 1")
+    ptr, pitch = _rows(scores, "scores")
+    m, I = int(scores.shape[0]), int(scores.shape[1])
+    if m > 1 and scores.stride(0) < I:
+        raise ValueError(f"scores: rows overlap (stride {scores.stride(0)} below {I} columns)")
+    topk = min(topk, I)                     # as full_rank_users: argsort(...)[:topk] truncates
+    if exclude is not None and row_users is None:
+        raise ValueError("rank_rows_f32: an exclusion needs row_users (the CSR row of every score row)")
+    indptr = items = None
+    if row_users is not None:
+        row_users = torch.as_tensor(row_users).to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+        if row_users.numel() != m:
+            raise ValueError(f"row_users: {row_users.numel()} entries for {m} score rows")
+    if exclude is not None:
+        indptr, items = exclude
+        U = int(indptr.numel()) - 1
+        if items.numel() == 0:              # (an empty tensor has no pointer to hand over)
+            items = torch.zeros(1, dtype=torch.int32, device=scores.device)
+        if m and validate:
+            lo, hi = (int(x) for x in torch.stack([row_users.min(), row_users.max()]).tolist())
+            if lo < 0 or hi >= U:
+                raise IndexError(f"index {hi if hi >= U else lo} is out of bounds for the user table with {U} rows")
+            _check_exclusion(indptr, exclude[1], U)
+    if out is not None:
+        ids, sc = out
+    else:
+        ids = torch.empty(m, topk, dtype=torch.int64, device=scores.device)
+        sc = torch.empty(m, topk, dtype=torch.float32, device=scores.device) if return_scores else None
+    if ids.shape != (m, topk) or (sc is not None and sc.shape != (m, topk)):
+        raise ValueError(f"out: expected [{m}, {topk}] tensors")
+    if m:
+        check(lib.daisy_rank_rows_f32(ptr, m, I, pitch, _ptr(row_users if exclude is not None else None, torch.int64, "row_users"),
+                                      _ptr(indptr, torch.int64, "exclude indptr"), _ptr(items, torch.int32, "exclude items"),
+                                      topk, _ptr(ids, torch.int64, "ids"), _ptr(sc, torch.float32, "scores"), _stream()))
+    return (ids, sc) if return_scores else ids
 
 
 # ---- MostPop and the ranking KPIs (csrc/pop.hip, csrc/metrics.hip; DESIGN.md §20) ----------------------------------------

@@ -20,4 +20,4 @@ if not os.path.exists(LIB_PATH):
 torch.ops.load_library(LIB_PATH)
 OPS = ("mf_predict", "mf_rank_topk", "mf_full_rank", "sample_uniform_neg", "bpr_mf_step", "ngcf_layer_fwd",
        "ngcf_layer_bwd", "nfm_scores", "vae_scores", "ease_full_rank_users", "slim_full_rank_users", "knn_full_rank_users",
-       "psvd_full_rank_users")
+       "psvd_full_rank_users", "rank_rows_f32")

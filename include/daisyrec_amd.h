@@ -576,6 +576,13 @@ int daisy_neumf_ctx_set_precision(daisy_neumf_ctx *ctx, int32_t bf16_gemm);
  *   users i64[1], items == NULL, C == 0                  full_rank (:211-233): item of pair e = e   */
 int daisy_neumf_scores(daisy_neumf_ctx *ctx, const daisy_neumf_params *params, const int64_t *users,
                        const int64_t *items, int64_t n, int64_t C, float *out, daisy_stream_t stream);
+/* "These users x all items" (additive to ABI 8): out f32[m][item_num], out[b][i] = the eval-mode score of
+ * (users[b], i), users i64[m] in any order, duplicates allowed.  The m * item_num pairs run through the forward code of
+ * daisy_neumf_scores in pieces of max_rows - pair e = (users[e / item_num], e % item_num), formed in the gather: no
+ * candidate array of m * item_num ids exists.  A pair's score is computed by the same instructions as there; in the
+ * bf16 levels its bits depend on the piece's row count exactly as they do there (level 2 needs whole 128-row tiles). */
+int daisy_neumf_scores_users(daisy_neumf_ctx *ctx, const daisy_neumf_params *params, const int64_t *users, int64_t m,
+                             float *out, daisy_stream_t stream);
 /* One training batch of NeuMF.calc_loss + backward (:139-169): rows (u, i, j) int32[B] (point-wise
  * losses: j = label).  ACCUMULATES the dense gradients into `grads` (same table layout; zero before
  * the first step, the optimiser kernels below clear what they consume) and writes stats.
@@ -859,6 +866,13 @@ int daisy_nfm_fit_epoch(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, cons
 int daisy_nfm_scores(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_bn_state *bn, const int64_t *users,
                      const int64_t *items, int64_t n, int64_t C, int32_t train, float dropout_p, uint64_t seed, float *out,
                      daisy_stream_t stream);
+/* "These users x all items" in eval mode only (additive to ABI 8): out f32[m][item_num], out[b][i] = the
+ * score daisy_nfm_scores (train == 0) gives the pair (users[b], i), from the same fused kernel - a pair's score depends on
+ * the pair alone, so the bits do not depend on m.  users i64[m], any order, duplicates allowed; pair e = (users[e /
+ * item_num], e % item_num) is formed in the kernel: no candidate array of m * item_num ids exists.  Running statistics
+ * are read, never written. */
+int daisy_nfm_scores_users(daisy_nfm_ctx *ctx, const daisy_nfm_params *params, const daisy_nfm_bn_state *bn,
+                           const int64_t *users, int64_t m, float *out, daisy_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Multi-VAE (daisy/model/VAECFRecommender.py, VAECF).  Encoder [I] + hidden + [lat], decoder [lat/2] +
@@ -1160,7 +1174,28 @@ int daisy_psvd_full_rank_users(const double *user_vec, const double *item_vec, i
                                int32_t topk, int64_t *out_ids, double *out_scores, daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * MostPop (daisy/model/PopRecommender.py) and the ranking KPIs (daisy/utils/metrics.py): csrc/pop.hip, csrc/metrics.hip;
+ * Masked top-k over rows of fp32 scores (csrc/rank_rows.hip; additive to ABI 8): the selector of
+ * full_rank_users for NeuMF, NFM and Multi-VAE, whose scores come out of kernels of their own
+ * ---------------------------------------------------------------------- */
+/* For every row r < m of scores (row r = scores[r * pitch .. + item_num), pitch >= item_num) the topk items, best first:
+ * score descending, a NaN first, -0.0 equal to +0.0, equal scores by ascending item id - daisy_full_rank_users' order.
+ * One launch of one 256-thread workgroup per row; float4 loads when scores is 16-byte aligned and pitch % 4 == 0, element
+ * loads otherwise (chosen once per launch; the result is the same).  excl_indptr int64 [user_num + 1] / excl_items int32
+ * (ascending inside a row, duplicates allowed: what daisy_build_user_csr returns; both or none) drop the items of CSR row
+ * row_users[r] from row r; row_users int64 [m] (any order, duplicates allowed) may be NULL only without an exclusion.  Row
+ * contents are only compared, never used as an index: an unsorted row or an entry >= item_num may cost missed exclusions,
+ * never an out-of-bounds access; row_users and excl_indptr are the caller's to validate.  out_ids int64 [m, topk];
+ * out_scores fp32 [m, topk] or NULL holds the row's own stored value at the selected id (re-read, not decoded: a NaN keeps
+ * its payload, a zero its sign); positions beyond a row's eligible items hold id -1 and score -inf.  1 <= topk <=
+ * min(item_num, 128): a larger topk is DAISY_ERR_ARG with the cap in the message.  Every argument is checked before the
+ * first HIP call; m == 0 returns DAISY_OK without a launch.  No workspace, no global or floating-point atomics: the
+ * candidates of a row live in LDS, their order is total, and two runs give the same bits. */
+int daisy_rank_rows_f32(const float *scores, int64_t m, int64_t item_num, int64_t pitch, const int64_t *row_users,
+                        const int64_t *excl_indptr, const int32_t *excl_items, int32_t topk, int64_t *out_ids,
+                        float *out_scores, daisy_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * MostPop(daisy/model/PopRecommender.py) and the ranking KPIs (daisy/utils/metrics.py): csrc/pop.hip, csrc/metrics.hip;
  * DESIGN.md §20.
  * ---------------------------------------------------------------------- */
 /* PopRecommender.py:30-33 (fit): cnt int64 [item_num] = the occurrences of every id in items [nnz] (int32, or int64 when
