@@ -110,6 +110,7 @@ KNN_MODES = {"cosine": 0, "asymmetric": 1, "tanimoto": 2, "dice": 3, "tversky": 
 KPI_IDS = {"precision": 0, "recall": 1, "hit": 2, "mrr": 3, "map": 4, "ndcg": 5, "f1": 6, "auc": 7, "popularity": 8,
            "diversity": 9, "coverage": 10}
 KPI_PER_USER = 10
+KPI_FULL_AUC = 11        # daisy_position_kpis only: the exact AUC over all eligible items
 METRICS_MAX_K, METRICS_MAX_CUTOFFS, METRICS_MAX_CATS = 256, 12, 256
 
 # name -> (restype, argtypes); every symbol include/daisyrec_amd.h declares
@@ -187,6 +188,9 @@ SIGNATURES = {
     "daisy_fm_full_rank": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _i32, _p, _p, _sz, _p]),
     "daisy_full_rank_users_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "daisy_full_rank_users": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "daisy_full_rank_positions_workspace_bytes": (_sz, [_i64, _i64]),
+    "daisy_full_rank_positions": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p,
+                                             _sz, _p]),
     "daisy_neumf_ctx_create": (C.c_int, [C.POINTER(_p), _i64, _i32, _i32, _i32, _i64, _i64]),
     "daisy_neumf_ctx_destroy": (C.c_int, [_p]),
     "daisy_neumf_ctx_bytes": (_sz, [_p]),
@@ -280,6 +284,8 @@ SIGNATURES = {
     "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),
     "daisy_ranking_kpis": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _i64, _p, _i32,
                                      _i32, _p, C.c_uint32, _p, _p, _p, _p, _sz, _p]),
+    "daisy_position_kpis_workspace_bytes": (_sz, [_i64, _i32, C.c_uint32]),
+    "daisy_position_kpis": (C.c_int, [_p, _p, _p, _p, _i64, C.POINTER(_i32), _i32, _p, _p, _i64, C.c_uint32, _p, _p, _p, _sz, _p]),
     "daisy_prep_encode": (C.c_int, [_p, _i64, _p, _p, C.POINTER(_i64), _p]),
     "daisy_prep_process": (C.c_int, [_p, _p, _p, _p, _i64, _i32, C.c_double, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p,
                                      C.POINTER(_i64), _p]),

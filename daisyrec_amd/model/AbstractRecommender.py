@@ -104,6 +104,12 @@ class AbstractRecommender(nn.Module):
         raise NotImplementedError(f"{type(self).__name__} has no full_rank_users: the thirteen models that implement it "
                                   "are listed in DESIGN.md §24-§26")
 
+    def full_rank_positions(self, users, targets, exclude=None, **kw):
+        """The exact rank of every held-out item among all eligible items (no counterpart in the reference; DESIGN.md
+        §27): the models that score by a dot product of two fp32 tables implement it."""
+        raise NotImplementedError(f"{type(self).__name__} has no full_rank_positions: MF, FM, LightGCN, NGCF and Item2Vec "
+                                  "implement it (DESIGN.md §27)")
+
     # the score chunk of _full_rank_users_scored: the best of the 16 / 64 / 256 MiB measured (DESIGN.md §26) - a score call has
     # a fixed cost that larger chunks spread over more users (Multi-VAE's first encoder layer above all)
     SCORED_CHUNK_BYTES = 256 << 20
@@ -150,6 +156,15 @@ class AbstractRecommender(nn.Module):
         (utils.user_csr) or a train_ur dict of sets, converted like build_candidates_set converts it."""
         users, exclude = self._users_and_exclusion(users, exclude, int(P.shape[0]), P.device)
         return ops.full_rank_users(P, Q, users, self.topk, exclude=exclude, biases=biases, return_scores=return_scores)
+
+    def _full_rank_positions(self, P, Q, users, targets, exclude, biases=None, **kw):
+        """full_rank_positions of a dot-product model over its tables: `targets` and `exclude` are an (indptr, items)
+        device CSR (utils.user_csr) or a dict of sets (test_ur / train_ur), converted as _full_rank_users converts
+        train_ur; kw: return_scores, return_eligible, item_slices, validate of ops.full_rank_positions."""
+        U = int(P.shape[0])
+        users, exclude = self._users_and_exclusion(users, exclude, U, P.device)
+        _, targets = self._users_and_exclusion(users, targets, U, P.device)
+        return ops.full_rank_positions(P, Q, users, targets, exclude=exclude, biases=biases, **kw)
 
     @staticmethod
     def _users_and_exclusion(users, exclude, user_num, device):

@@ -118,6 +118,11 @@ class Item2Vec(GeneralRecommender):
         Uemb, S = self._tables()
         return ops.mf_full_rank(Uemb, S, int(u), self.topk).cpu().numpy()
 
+    def full_rank_positions(self, users, targets, exclude=None, **kw):
+        """exact ranks of held-out items over the user and item tables (MF.full_rank_positions)"""
+        Uemb, S = self._tables()
+        return self._full_rank_positions(Uemb, S, users, targets, exclude, **kw)
+
     def full_rank_users(self, users, exclude=None, return_scores=False):
         """full ranking of many users over the user and item tables (MF.full_rank_users)"""
         Uemb, S = self._tables()

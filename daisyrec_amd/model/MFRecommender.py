@@ -162,6 +162,13 @@ class MF(GeneralRecommender):
         P, Q = self._tables()
         return ops.mf_full_rank(P, Q, int(u), self.topk, biases=self._biases()).cpu().numpy()
 
+    def full_rank_positions(self, users, targets, exclude=None, **kw):
+        """The exact 0-based rank of every item of the users' rows of `targets` (a device CSR of utils.user_csr or a
+        test_ur dict of sets) among all items outside their rows of `exclude`, in full_rank_users' order and without
+        its cap on topk: (out_indptr, positions[, scores][, eligible]) of ops.full_rank_positions."""
+        P, Q = self._tables()
+        return self._full_rank_positions(P, Q, users, targets, exclude, biases=self._biases(), **kw)
+
     def full_rank_users(self, users, exclude=None, return_scores=False):
         """The full-ranking protocol for many users in two launches: device int64 [n, min(topk, I)],
         each row what full_rank(u) returns once the items of the user's row of `exclude` (None, an (indptr, items)

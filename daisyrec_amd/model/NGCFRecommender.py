@@ -296,6 +296,11 @@ class NGCF(GeneralRecommender):
         ue, ie = self._restore()
         return ops.mf_full_rank(ue, ie, int(u), self.topk).cpu().numpy()
 
+    def full_rank_positions(self, users, targets, exclude=None, **kw):
+        """exact ranks of held-out items over the propagated embeddings (MF.full_rank_positions)"""
+        ue, ie = self._restore()
+        return self._full_rank_positions(ue, ie, users, targets, exclude, **kw)
+
     def full_rank_users(self, users, exclude=None, return_scores=False):
         """full ranking of many users over the propagated embeddings (MF.full_rank_users)"""
         ue, ie = self._restore()

@@ -761,6 +761,124 @@ def full_rank_users(P, Q, users, topk, exclude=None, biases=None, return_scores=
     return (ids, scores) if return_scores else ids
 
 
+def _check_targets(indptr, items, user_num):
+    """_check_exclusion for the target CSR of full_rank_positions, whose rows must ascend STRICTLY: a duplicate target
+    would be two outputs of one item."""
+    if indptr.dim() != 1 or items.dim() != 1 or indptr.numel() != user_num + 1:
+        raise ValueError(f"targets: indptr has {indptr.numel()} entries, the user table has {user_num} rows "
+                         f"(expected {user_num + 1})")
+    nnz = items.numel()
+    if not bool(((indptr[1:] >= indptr[:-1]).all() & (indptr[0] == 0) & (indptr[-1] == nnz)).item()):
+        raise ValueError(f"targets: indptr must rise from 0 to len(items) = {nnz}")
+    if nnz > 1:
+        inside = torch.ones(nnz + 1, dtype=torch.bool, device=items.device)
+        inside[indptr] = False
+        down, same = ((items[1:] < items[:-1]) & inside[1:nnz]).any(), ((items[1:] == items[:-1]) & inside[1:nnz]).any()
+        down, same = torch.stack([down, same]).tolist()
+        if down:
+            raise ValueError("targets: the items of a row must be ascending (utils.user_csr / ops.build_user_csr sort them)")
+        if same:
+            raise ValueError("targets: a row holds the same item twice")
+
+
+def full_rank_positions(P, Q, users, targets, exclude=None, biases=None, return_scores=False, return_eligible=False,
+                        item_slices=0, validate=True):
+    """The exact 0-based rank of every held-out item among ALL eligible items (csrc/rank_positions.hip):
+    for request b = users[b] and every item t of the user's row of `targets` = (indptr int64 [U + 1], items int32
+    ascending per row), the number of items outside the user's row of `exclude` whose (score, id) comes before t's in
+    full_rank_users' order - bit for bit the index full_rank_users would list t at, without its cap on topk.  ->
+    (out_indptr int64 [n + 1], positions int32 [T][, scores float32 [T]][, eligible int32 [n]]): request b's targets in
+    row order at out_indptr[b] .. out_indptr[b + 1]; -1 (score -inf) for a target outside [0, I) or inside the exclusion
+    row; eligible = the items a user can be recommended.  validate: full_rank_users' checks on users, exclude and
+    targets (one read-back each; duplicate targets in a row are a ValueError); False skips them - the kernels then trust
+    the ids and the indptr arrays, only compare the exclusion's contents and range-check every target id."""
+    U, I = int(P.shape[0]), int(Q.shape[0])
+    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1]:
+        raise ValueError(f"full_rank_positions: P {tuple(P.shape)} and Q {tuple(Q.shape)} need the same column count")
+    dev = P.device
+    users = torch.as_tensor(users).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    n = users.numel()
+    t_indptr, t_items = targets
+    indptr = items = None
+    if exclude is not None:
+        indptr, items = exclude
+        if items.numel() == 0:              # (an empty tensor has no pointer to hand over)
+            items = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n and validate:
+        lo, hi = (int(x) for x in torch.stack([users.min(), users.max()]).tolist())
+        if lo < 0 or hi >= U:
+            raise IndexError(f"index {hi if hi >= U else lo} is out of bounds for the user table with {U} rows")
+        if exclude is not None:
+            _check_exclusion(indptr, exclude[1], U)
+        _check_targets(t_indptr, t_items, U)
+    elif t_indptr.numel() != U + 1:
+        raise ValueError(f"targets: indptr has {t_indptr.numel()} entries, the user table has {U} rows (expected {U + 1})")
+    out_indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(t_indptr[users + 1] - t_indptr[users], 0, out=out_indptr[1:])
+    T = int(out_indptr[-1]) if n else 0
+    pos = torch.empty(T, dtype=torch.int32, device=dev)
+    scores = torch.empty(T, dtype=torch.float32, device=dev) if return_scores else None
+    eligible = torch.empty(n, dtype=torch.int32, device=dev) if return_eligible else None
+    if n and (T or return_eligible):
+        if t_items.numel() == 0:
+            t_items = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _ws(lib.daisy_full_rank_positions_workspace_bytes(n, T), dev)
+        bu, bi, b0 = _bias_ptrs(biases)
+        dummy = pos if T else torch.zeros(1, dtype=torch.int32, device=dev)
+        check(lib.daisy_full_rank_positions(_ptr(P, torch.float32, "P"), _ptr(Q, torch.float32, "Q"), bu, bi, b0, P.shape[1], I,
+                                            _ptr(users, torch.int64, "users"), n, _ptr(indptr, torch.int64, "exclude indptr"),
+                                            _ptr(items, torch.int32, "exclude items"),
+                                            _ptr(t_indptr, torch.int64, "targets indptr"),
+                                            _ptr(t_items, torch.int32, "targets items"),
+                                            _ptr(out_indptr, torch.int64, "out_indptr"), T, int(item_slices),
+                                            _ptr(dummy, torch.int32, "positions"), _ptr(scores, torch.float32, "scores"),
+                                            _ptr(eligible, torch.int32, "eligible"), _ptr(ws, torch.uint8, "ws"), ws.numel(),
+                                            _stream()))
+    out = (out_indptr, pos)
+    if return_scores:
+        out += (scores,)
+    if return_eligible:
+        out += (eligible,)
+    return out
+
+
+POSITION_KPIS = ("precision", "recall", "hit", "mrr", "map", "ndcg", "f1", "auc", "full_auc")
+
+
+def position_kpis(out_indptr, positions, gt_len, eligible, cutoffs, metrics, disc=None, disc_cum=None, per_user=False):
+    """daisy_position_kpis: the per-list KPIs of ranking_kpis (and 'full_auc') at every cutoff - any K >= 1 - from
+    full_rank_positions' outputs.  gt_len int64 [n] (None: the row lengths), eligible int32 [n]; disc float64 = 1 /
+    log2(p + 2) and disc_cum, its running sum, for every position below the largest cutoff (needed for ndcg, built on
+    the host like ranking_kpis' disc).  -> (names in slot order, per_user float64 [len(names), nc, n] or None, means
+    float64 [len(names), nc])."""
+    mask = 0
+    for name in metrics:
+        if name in ("popularity", "diversity", "coverage"):
+            raise ValueError(f"'{name}' needs the ranked lists: use full_rank_users + ranking_kpis")
+        if name not in POSITION_KPIS:
+            raise ValueError(f"Invalid metric name {name}")
+        mask |= 1 << (N.KPI_FULL_AUC if name == "full_auc" else N.KPI_IDS[name])
+    names = [m for m in POSITION_KPIS if m in metrics]
+    dev = positions.device
+    n, nc = out_indptr.numel() - 1, len(cutoffs)
+    cuts = (C.c_int32 * max(nc, 1))(*[int(k) for k in cutoffs])
+    out_user = torch.empty(len(names), nc, n, dtype=torch.float64, device=dev) if per_user else None
+    means = torch.empty(len(names), nc, dtype=torch.float64, device=dev)
+    if "ndcg" in metrics and (disc is None or disc_cum is None or disc.numel() != disc_cum.numel()):
+        raise ValueError("'ndcg' needs disc and disc_cum, of one length")
+    disc_len = 0 if disc is None else disc.numel()
+    if positions.numel() == 0:
+        positions = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _ws(lib.daisy_position_kpis_workspace_bytes(n, nc, mask), dev)
+    check(lib.daisy_position_kpis(_ptr(out_indptr, torch.int64, "out_indptr"), _ptr(positions, torch.int32, "positions"),
+                                  _ptr(gt_len, torch.int64, "gt_len"), _ptr(eligible, torch.int32, "eligible"), n, cuts, nc,
+                                  _ptr(disc, torch.float64, "disc"), _ptr(disc_cum, torch.float64, "disc_cum"), disc_len, mask,
+                                  _ptr(out_user, torch.float64, "per_user"), _ptr(means, torch.float64, "means"),
+                                  _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return names, out_user, means
+
+
 def build_user_csr(users, items, user_num):
     """get_ur (utils.py:19-34) as a device CSR: (indptr int64[U+1], sorted items int32[n])."""
     n = users.numel()

@@ -316,3 +316,69 @@ def calc_ranking_results(test_ur, pred_ur, test_u, config):
         res[topk] = np.array(kpis)
 
     return res
+
+
+def position_kpis(out_indptr, positions, gt_len, eligible, cutoffs, metrics, per_user=False):
+    """ranking_kpis from the exact rank positions of the held-out items (ops.full_rank_positions): every
+    per-list KPI of `metrics` - 'precision', 'recall', 'hit', 'mrr', 'map', 'ndcg', 'f1', 'auc', with the reference's list
+    definitions applied to the implied list of length K, and 'full_auc', the exact AUC over all eligible items - at
+    every cutoff (strictly ascending, ANY K >= 1) in one device call.  gt_len: the truths of every request (None: the
+    length of its row).  Where K exceeds a user's eligible items the implied list is that short: precision and auc
+    use min(K, eligible).  'popularity', 'diversity' and 'coverage' need the lists and raise ValueError.  -> the dict
+    of ranking_kpis ('coverage_counts' is None)."""
+    metrics = list(dict.fromkeys(metrics))
+    cutoffs = [int(k) for k in cutoffs]
+    dev = positions.device
+    if gt_len is not None:
+        gt_len = torch.as_tensor(gt_len).to(device=dev, dtype=torch.int64).contiguous()
+    eligible = torch.as_tensor(eligible).to(device=dev, dtype=torch.int32).contiguous()
+    disc = cum = None
+    if "ndcg" in metrics:                   # the discounts of every position a hit can have, as ranking_kpis builds them
+        top = int(positions.max()) + 1 if positions.numel() else 0
+        d_np = 1 / np.log2(np.arange(2, max(1, min(max(cutoffs, default=1), top)) + 2))
+        disc, cum = torch.from_numpy(d_np).to(dev), torch.from_numpy(np.cumsum(d_np)).to(dev)
+    names, pu, means = ops.position_kpis(out_indptr, positions.contiguous(), gt_len, eligible, cutoffs, metrics, disc=disc,
+                                         disc_cum=cum, per_user=per_user)
+    means_h = means.cpu().numpy()
+    out = {"cutoffs": cutoffs, "means": {nm: means_h[s] for s, nm in enumerate(names)}, "per_user": None,
+           "coverage_counts": None}
+    if per_user:
+        pu_h = pu.cpu().numpy()
+        out["per_user"] = {nm: pu_h[s] for s, nm in enumerate(names)}
+    return out
+
+
+def calc_full_ranking_results(model, test_ur, train_ur, config):
+    """calc_ranking_results under the full-ranking protocol, from ONE model.full_rank_positions call over the users of
+    test_ur (every item outside the user's train_ur row is a candidate) and one KPI call: the same DataFrame - the
+    columns 'KPI@K', 1, 5, 10, 20, 30, 50 and config['topk'], those above config['topk'] skipped - and the same @10 log
+    lines.  config['topk'] has no upper bound here, and a user with fewer eligible items than a cutoff is not refused
+    (position_kpis).  config['metrics'] may hold 'full_auc'."""
+    import pandas as pd
+    logger = config['logger']
+    path = config['res_path']
+    if not os.path.exists(path):
+        os.makedirs(path)
+    names = dict(metrics_name_config, full_auc='AUC (all items)')
+    for mc in config['metrics']:
+        if mc not in names:
+            raise ValueError(f'Invalid metric name {mc}')
+    users = np.asarray(list(test_ur.keys()), dtype=np.int64)
+    for u in users.tolist():
+        if len(test_ur[u]) == 0:
+            raise ValueError(f"user {u} of test_u has no ground truth in test_ur")
+    res = pd.DataFrame({'KPI@K': [names[kpi_name] for kpi_name in config['metrics']]})
+    common_ks = [1, 5, 10, 20, 30, 50]
+    if config['topk'] not in common_ks:
+        common_ks.append(config['topk'])
+    order = [topk for topk in common_ks if topk <= config['topk']]
+    ks = sorted(order)
+    out_indptr, pos, eligible = model.full_rank_positions(users, test_ur, exclude=train_ur, return_eligible=True)
+    means = position_kpis(out_indptr, pos, None, eligible, ks, config['metrics'])["means"]
+    for topk in order:
+        kpis = [np.float64(means[mc][ks.index(topk)]) for mc in config['metrics']]
+        if topk == 10:
+            for kpi_name, kpi_res in zip(config['metrics'], kpis):
+                logger.info(f'{names[kpi_name]}@{topk}: {kpi_res:.4f}')
+        res[topk] = np.array(kpis)
+    return res

@@ -460,6 +460,29 @@ int daisy_full_rank_users(const float *P, const float *Q, const float *u_bias, c
                           int32_t d, int64_t item_num, const int64_t *users, int64_t n, const int64_t *excl_indptr,
                           const int32_t *excl_items, int32_t topk, int32_t item_slices, int64_t *out_ids,
                           float *out_scores, void *workspace, size_t workspace_bytes, daisy_stream_t stream);
+/* Exact ranks of held-out items over all items (csrc/rank_positions.hip; additive to ABI 8).  P, Q, the
+ * bias triple, d, item_num, users [n], the exclusion CSR and item_slices are daisy_full_rank_users'.  t_indptr int64
+ * [user_num + 1] / t_items int32: the TARGET CSR over all users, ascending inside a row (daisy_build_user_csr's).
+ * out_indptr int64 [n + 1]: the prefix sum of the target-row lengths of users[0 .. n), built by the caller; n_targets =
+ * out_indptr[n].  With word(u, j) = (key of the fp32 score << 32) | (0xFFFFFFFF - j) of daisy_full_rank_users and E_u the
+ * items of [0, item_num) outside u's exclusion row, request b's target number r (row order) gets
+ *   out_pos[out_indptr[b] + r]   int32: #{ j in E_u : word(u, j) > word(u, t) } - its 0-based rank, score descending, a
+ *                                NaN first, equal scores by ascending id; -1 for a target outside [0, item_num) (it is
+ *                                range-checked before it indexes anything) or inside the exclusion row
+ *   out_scores[...]              fp32 or NULL: the target's score, bit for bit daisy_full_rank_users'; -inf where pos = -1
+ *   out_eligible[b]              int32 or NULL: |E_u|
+ * so that with the same arguments daisy_full_rank_users' ids[b][pos] == t for every target with 0 <= pos < topk.  There
+ * is no cap on the row length (a row is split into blocks of 32 targets on the device).  The counts are integer atomics:
+ * the result does not depend on item_slices, the schedule or the run, bit for bit.  Row contents of the exclusion are
+ * only compared; user ids, the indptr arrays and out_indptr are the caller's to validate.  Every argument is checked
+ * before the first HIP call. */
+size_t daisy_full_rank_positions_workspace_bytes(int64_t n, int64_t n_targets);
+int daisy_full_rank_positions(const float *P, const float *Q, const float *u_bias, const float *i_bias, const float *bias,
+                              int32_t d, int64_t item_num, const int64_t *users, int64_t n, const int64_t *excl_indptr,
+                              const int32_t *excl_items, const int64_t *t_indptr, const int32_t *t_items,
+                              const int64_t *out_indptr, int64_t n_targets, int32_t item_slices, int32_t *out_pos,
+                              float *out_scores, int32_t *out_eligible, void *workspace, size_t workspace_bytes,
+                              daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Uniform negative sampler (sampler.py:55-103, uniform branch :82-89)
@@ -1259,6 +1282,25 @@ int daisy_ranking_kpis(const void *pred, int32_t pred_is_i64, int64_t n, int32_t
                        int32_t cat_words, int32_t n_cats, const double *sqrt_tab, uint32_t metrics, double *per_user,
                        double *means, int64_t *cover_counts, void *workspace, size_t workspace_bytes,
                        daisy_stream_t stream);
+
+/* The per-list KPIs of daisy_ranking_kpis from rank positions (csrc/metrics_positions.hip): the
+ * reference's list definitions applied to the implied list of length K, at ANY K >= 1.  out_indptr int64 [n + 1] /
+ * positions int32: daisy_full_rank_positions' outputs (-1: not ranked); gt_len int64 [n] or NULL: the truths of a request
+ * (NULL: its row length); eligible int32 [n].  cutoffs_host as in daisy_ranking_kpis without the upper bound.  metrics:
+ * bits DAISY_KPI_PRECISION .. DAISY_KPI_AUC and DAISY_KPI_FULL_AUC; any other bit is DAISY_ERR_ARG (popularity, diversity
+ * and coverage need the lists).  disc fp64 [disc_len] = 1 / log2(p + 2) and disc_cum = its running sum, built on the host
+ * (needed for ndcg; disc_len > every position below the largest cutoff).  With h the positions < K, r the rank of a hit
+ * among the hits, Ke = min(K, eligible): precision h / Ke; recall h / gt_len; hit; mrr 1 / (min pos + 1) if < K; map the
+ * mean over the hits of (r + 1) / (pos + 1); ndcg sum disc[pos] / disc_cum[h - 1]; f1 2 pre rec / (pre + rec); auc sum
+ * over the hits of ((Ke - 1 - pos) - (h - 1 - r)) / (h (Ke - h)); full_auc, the same at every cutoff, sum over the T'
+ * ranked targets of ((E - T') - (pos - r)) / (T' (E - T')).  0 / 0 is NaN, as in daisy_ranking_kpis.  Outputs as there:
+ * per_user fp64 [slots, nc, n] or NULL, means fp64 [slots, nc]; slots in bit order.  Sums run in a fixed order. */
+#define DAISY_KPI_FULL_AUC 11
+size_t daisy_position_kpis_workspace_bytes(int64_t n, int32_t nc, uint32_t metrics);
+int daisy_position_kpis(const int64_t *out_indptr, const int32_t *positions, const int64_t *gt_len, const int32_t *eligible,
+                        int64_t n, const int32_t *cutoffs_host, int32_t nc, const double *disc, const double *disc_cum,
+                        int64_t disc_len, uint32_t metrics, double *per_user, double *means, void *workspace,
+                        size_t workspace_bytes, daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Preprocessor.process (daisy/utils/loader.py:176-189) and split_test / split_validation (daisy/utils/splitter.py):
