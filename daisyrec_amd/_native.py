@@ -279,6 +279,15 @@ SIGNATURES = {
                                             _p]),
     "daisy_psvd_full_rank_users": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p, _i32, _p, _p, _p]),
     "daisy_rank_rows_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p]),
+    # exact ranks of held-out items: the sibling's operands, then users, n, the exclusion CSR, the target CSR,
+    # out_indptr, n_targets, out_pos, out_scores, out_eligible[, path], stream
+    "daisy_ease_full_rank_positions": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "daisy_slim_full_rank_positions": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
+                                                 _p, _i32, _p]),
+    "daisy_knn_full_rank_positions": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p,
+                                                _p, _p, _i32, _p]),
+    "daisy_psvd_full_rank_positions": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "daisy_rank_rows_positions_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "daisy_pop_fit":(C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
     "daisy_pop_rank": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
     "daisy_ranking_kpis_workspace_bytes": (_sz, [_i64, _i32, _i64, C.c_uint32]),

@@ -105,10 +105,15 @@ class AbstractRecommender(nn.Module):
                                   "are listed in DESIGN.md §24-§26")
 
     def full_rank_positions(self, users, targets, exclude=None, **kw):
-        """The exact rank of every held-out item among all eligible items (no counterpart in the reference; DESIGN.md
-        §27): the models that score by a dot product of two fp32 tables implement it."""
-        raise NotImplementedError(f"{type(self).__name__} has no full_rank_positions: MF, FM, LightGCN, NGCF and Item2Vec "
-                                  "implement it (DESIGN.md §27)")
+        """The exact rank of every held-out item among all eligible items (no counterpart in the reference): eleven
+        models implement it - those that score by a dot product of two fp32 tables (MF, FM, LightGCN, NGCF, Item2Vec;
+        DESIGN.md §27), SLiM, ItemKNNCF, UserKNNCF and PureSVD on their fp64 sums, and NFM and VAECF on rows of their own
+        scores.  EASE and NeuMF follow: what they need is there at the ops level
+        (ops.ease_full_rank_positions, ops.rank_rows_positions_f32)."""
+        raise NotImplementedError(f"{type(self).__name__} has no full_rank_positions: MF, FM, LightGCN, NGCF, Item2Vec "
+                                  "(DESIGN.md §27), SLiM, ItemKNNCF, UserKNNCF, PureSVD, NFM and VAECF (§28) implement it; "
+                                  "EASE and NeuMF follow (ops.ease_full_rank_positions and ops.rank_rows_positions_f32 "
+                                  "are there)")
 
     # the score chunk of _full_rank_users_scored: the best of the 16 / 64 / 256 MiB measured (DESIGN.md §26) - a score call has
     # a fixed cost that larger chunks spread over more users (Multi-VAE's first encoder layer above all)
@@ -150,6 +155,34 @@ class AbstractRecommender(nn.Module):
                 ops.rank_rows_f32(chunk, topk, row_users=us, exclude=exclude, validate=False,
                                   out=(ids[b0:b1], None if scores is None else scores[b0:b1]))
         return (ids, scores) if return_scores else ids
+
+    def _full_rank_positions_scored(self, users, targets, exclude, chunk_bytes, user_num, item_num, device, make_scorer,
+                                    return_scores=False, return_eligible=False, validate=True):
+        """full_rank_positions of a model whose scores come out of a kernel of its own, the twin of
+        _full_rank_users_scored: the same make_scorer closures, the same chunks of rows = max(1, chunk_bytes // (4 I))
+        users - per chunk one score call into a reused [rows, I] float32 buffer and one ops.rank_rows_positions_f32 into
+        the chunk's slice of the outputs.  `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets, as
+        _full_rank_positions takes them; the checks of ops.full_rank_positions run once, for all chunks (validate=False
+        skips them).  -> ops.full_rank_positions' tuple."""
+        users, exclude = self._users_and_exclusion(users, exclude, user_num, device)
+        _, targets = self._users_and_exclusion(users, targets, user_num, device)
+        # the checks, out_indptr and the outputs of the whole request; the chunks write into slices of them
+        users, n, T, _ptrs, out_indptr, pos, scores, eligible, _keep = ops._rank_positions_args(
+            users, user_num, targets, exclude, return_scores, return_eligible, validate, device, torch.float32)
+        I = int(item_num)
+        if n and (T or return_eligible):
+            nbytes = self.SCORED_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+            rows = min(n, max(1, nbytes // (4 * I)))
+            score = make_scorer(users, rows)
+            buf = torch.empty(rows, I, dtype=torch.float32, device=device)
+            for b0 in range(0, n, rows):
+                b1 = min(n, b0 + rows)
+                us, chunk = users[b0:b1], buf[:b1 - b0]
+                score(us, b0, b1, chunk)
+                ops.rank_rows_positions_f32(chunk, us, targets, exclude=exclude, validate=False,
+                                            out=(out_indptr[b0:b1 + 1], pos, scores,
+                                                 None if eligible is None else eligible[b0:b1]))
+        return ops._rank_positions_out(out_indptr, pos, scores, eligible)
 
     def _full_rank_users(self, P, Q, users, exclude, return_scores, biases=None):
         """full_rank_users of a dot-product model over its tables: `exclude` is None, an (indptr, items) device CSR

@@ -292,8 +292,25 @@ class NFM(GeneralRecommender):
         call model.eval() first.  chunk_bytes (default 256 MiB) of scores at a time through daisy_nfm_scores_users, then
         ops.rank_rows_f32; the eval kernel computes a pair's score from the pair alone, so the result does not depend
         on chunk_bytes, bit for bit.  Nothing of the model changes: not the running statistics, not the score-call count."""
+        U, I, make_scorer = self._full_rank_scorer("full_rank_users")
+        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, I, self.device, make_scorer,
+                                            validate=validate)         # (validate: as in ops.full_rank_users)
+
+    def full_rank_positions(self, users, targets, exclude=None, chunk_bytes=None, **kw):
+        """The exact rank of every held-out item among all eligible items (no counterpart in the reference; DESIGN.md
+        §28): `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets (test_ur / train_ur); ->
+        ops.full_rank_positions' tuple, consistent with full_rank_users - its ids[b, pos] is the target wherever pos <
+        topk - without the cap on topk.  Eval mode only, and full_rank_users' chunks: per chunk one
+        daisy_nfm_scores_users call and one ops.rank_rows_positions_f32; the result does not depend on chunk_bytes, bit
+        for bit.  kw: return_scores, return_eligible, validate."""
+        U, I, make_scorer = self._full_rank_scorer("full_rank_positions")
+        return self._full_rank_positions_scored(users, targets, exclude, chunk_bytes, U, I, self.device, make_scorer, **kw)
+
+    def _full_rank_scorer(self, what):
+        """(user count, item count, make_scorer) of full_rank_users and full_rank_positions: the eval scores of a chunk of
+        users against all items through daisy_nfm_scores_users"""
         if self.training:
-            raise RuntimeError("NFM.full_rank_users ranks in eval mode only (running statistics, no dropout): call "
+            raise RuntimeError(f"NFM.{what} ranks in eval mode only (running statistics, no dropout): call "
                                "model.eval() first")
         p = self._params()
         bn = self._bn()
@@ -303,5 +320,4 @@ class NFM(GeneralRecommender):
         def make_scorer(us_all, rows):
             return lambda us, b0, b1, out: ctx.scores_users(p, bn, us, out)
 
-        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, I, self.device, make_scorer,
-                                            validate=validate)         # (validate: as in ops.full_rank_users)
+        return U, I, make_scorer

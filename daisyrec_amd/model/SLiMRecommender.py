@@ -148,6 +148,16 @@ class SLiM(GeneralRecommender):
         return ops.slim_full_rank_users(self._csr, self._W, self.item_num, users, self.topk, exclude=exclude,
                                         return_scores=return_scores)
 
+    def full_rank_positions(self, users, targets, exclude=None, **kw):
+        """The exact rank of every held-out item among all eligible items, in one launch (no counterpart in the
+        reference): `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets (test_ur /
+        train_ur); -> ops.full_rank_positions' tuple, consistent with full_rank_users - its ids[b, pos] is the target
+        wherever pos < topk - without the cap on topk.  kw: return_scores, return_eligible, validate, path."""
+        self._fitted()
+        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
+        _, targets = self._users_and_exclusion(users, targets, self.user_num, self.device)
+        return ops.slim_full_rank_positions(self._csr, self._W, self.item_num, users, targets, exclude=exclude, **kw)
+
     # -- the reference's attributes, built on demand -------------------------------------------------------------------
     @property
     def w_sparse(self):

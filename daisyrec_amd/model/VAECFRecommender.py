@@ -283,8 +283,26 @@ class VAECF(AERecommender):
         of a score depend on the chunk: the promise is per chunk - the chunk's lists are the exact ranking of what
         `_scores` returns for exactly that chunk's users in the same context.  Neither `update` nor the score-call count
         changes."""
+        U, make_scorer = self._full_rank_scorer("full_rank_users")
+        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, self.item_num, self.device,
+                                            make_scorer, validate=validate)
+
+    def full_rank_positions(self, users, targets, exclude=None, chunk_bytes=None, **kw):
+        """The exact rank of every held-out item among all eligible items (no counterpart in the reference; DESIGN.md
+        §28) - the full-ranking protocol Multi-VAE is defined under, without a cap on the cutoff: `targets` and `exclude`
+        are an (indptr, items) device CSR or a dict of sets (test_ur / train_ur); -> ops.full_rank_positions' tuple.  Eval
+        mode only, and full_rank_users' chunks: per chunk one daisy_vae_scores call and one ops.rank_rows_positions_f32, so
+        with the same chunk_bytes full_rank_users' ids[b, pos] is the target wherever pos < topk (a score's bits are per
+        chunk, as there).  kw: return_scores, return_eligible, validate."""
+        U, make_scorer = self._full_rank_scorer("full_rank_positions")
+        return self._full_rank_positions_scored(users, targets, exclude, chunk_bytes, U, self.item_num, self.device,
+                                                make_scorer, **kw)
+
+    def _full_rank_scorer(self, what):
+        """(user count, make_scorer) of full_rank_users and full_rank_positions: the scores of a chunk of users against all
+        items through daisy_vae_scores in the shared score context"""
         if self.training:
-            raise RuntimeError("VAECF.full_rank_users ranks in eval mode only (no dropout, no reparameterisation noise): "
+            raise RuntimeError(f"VAECF.{what} ranks in eval mode only (no dropout, no reparameterisation noise): "
                                "call model.eval() first")
         W = self._params()
         csr, lens = self._csr()
@@ -297,6 +315,5 @@ class VAECF(AERecommender):
             ctx = self._score_ctx(rows, max(entries))
             return lambda us, b0, b1, out: ctx.scores(W, csr, us, entries[b0 // rows], out=out)
 
-        return self._full_rank_users_scored(users, exclude, return_scores, chunk_bytes, U, self.item_num, self.device,
-                                            make_scorer, validate=validate)
+        return U, make_scorer
 

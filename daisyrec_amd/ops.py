@@ -2128,6 +2128,136 @@ def psvd_full_rank_users(user_vec, item_vec, users, topk, exclude=None, return_s
     return (ids, scores) if return_scores else ids
 
 
+# ---- exact ranks of held-out items on fp64 scores (csrc/rank_positions_f64.hip) ----------------------------
+RANK_COUNT_BLOCK = 512        # kRcTc (csrc/rank_count.h): targets a workgroup ranks per pass over the items (the tests' edges)
+
+
+def _rank_positions_request(users, user_num, targets, exclude, validate, device):
+    """The request of a *_full_rank_positions call, checked as ops.full_rank_positions checks it: -> (users int64 [n],
+    pointers (exclusion indptr, exclusion items, target indptr, target items), the tensors behind the pointers)."""
+    users = torch.as_tensor(users).to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+    n, U = users.numel(), int(user_num)
+    t_indptr, t_items = targets
+    indptr = items = None
+    if exclude is not None:
+        indptr, items = exclude
+        if items.numel() == 0:              # (an empty tensor has no pointer to hand over)
+            items = torch.zeros(1, dtype=torch.int32, device=device)
+    if n and validate:
+        lo, hi = (int(x) for x in torch.stack([users.min(), users.max()]).tolist())
+        if lo < 0 or hi >= U:
+            raise IndexError(f"index {hi if hi >= U else lo} is out of bounds for the user table with {U} rows")
+        if exclude is not None:
+            _check_exclusion(indptr, exclude[1], U)
+        _check_targets(t_indptr, t_items, U)
+    elif t_indptr.numel() != U + 1:
+        raise ValueError(f"targets: indptr has {t_indptr.numel()} entries, the user table has {U} rows (expected {U + 1})")
+    if t_items.numel() == 0:
+        t_items = torch.zeros(1, dtype=torch.int32, device=device)
+    ptrs = (_ptr(indptr, torch.int64, "exclude indptr"), _ptr(items, torch.int32, "exclude items"),
+            _ptr(t_indptr, torch.int64, "targets indptr"), _ptr(t_items, torch.int32, "targets items"))
+    return users, ptrs, (indptr, items, t_indptr, t_items)
+
+
+def _rank_positions_args(users, user_num, targets, exclude, return_scores, return_eligible, validate, device, score_dtype):
+    """What the *_full_rank_positions and rank_rows_positions_f32 share: _rank_positions_request and ops.full_rank_positions'
+    outputs.  -> (users int64 [n], n, T, the request's pointers, out_indptr, positions, scores or None, eligible or None,
+    the tensors behind the pointers)."""
+    users, ptrs, keep = _rank_positions_request(users, user_num, targets, exclude, validate, device)
+    n, t_indptr = users.numel(), targets[0]
+    out_indptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n:
+        torch.cumsum(t_indptr[users + 1] - t_indptr[users], 0, out=out_indptr[1:])
+    T = int(out_indptr[-1]) if n else 0
+    pos = torch.empty(T, dtype=torch.int32, device=device)
+    scores = torch.empty(T, dtype=score_dtype, device=device) if return_scores else None
+    eligible = torch.empty(n, dtype=torch.int32, device=device) if return_eligible else None
+    return users, n, T, ptrs, out_indptr, pos, scores, eligible, keep
+
+
+def _rank_positions_out(out_indptr, pos, scores, eligible):
+    out = (out_indptr, pos)
+    if scores is not None:
+        out += (scores,)
+    if eligible is not None:
+        out += (eligible,)
+    return out
+
+
+def ease_full_rank_positions(csr, W, users, targets, exclude=None, return_scores=False, return_eligible=False, validate=True):
+    """The exact 0-based rank of every held-out item among ALL eligible items by EASE's scores X[users] W, in one launch
+    (daisy_ease_full_rank_positions): for request b = users[b] and every item t of the user's row of
+    `targets` = (indptr int64 [U + 1], items int32 ascending per row), the number of items outside the user's row of
+    `exclude` whose float64 score is a number and comes before t's in ease_full_rank_users' order (score descending, equal
+    scores by ascending id) - the index ease_full_rank_users would list t at, without its cap on topk.  -> (out_indptr int64
+    [n + 1], positions int32 [T][, scores float64 [T]][, eligible int32 [n]]), ops.full_rank_positions' tuple: -1 (score
+    -inf) for a target outside [0, I) or inside the exclusion row, -1 (score NaN) for a target whose score is not a number;
+    eligible = the items a user can be recommended.  validate: ops.full_rank_positions' checks on users, exclude and
+    targets; False skips them - the kernel then trusts the user ids and the indptr arrays, only compares the exclusion's
+    contents and range-checks every target id.  No [n, I] array is written."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    wp, I = _ease_square(W, "W")
+    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
+        users, U, targets, exclude, return_scores, return_eligible, validate, W.device, torch.float64)
+    check(lib.daisy_ease_full_rank_positions(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), n, *ptrs,
+                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
+                                             _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
+                                             _stream()))
+    return _rank_positions_out(out_indptr, pos, scores, eligible)
+
+
+def slim_full_rank_positions(csr, W, item_num, users, targets, exclude=None, return_scores=False, return_eligible=False,
+                             validate=True, path="auto"):
+    """ease_full_rank_positions for SLiM (daisy_slim_full_rank_positions): the ranks are on slim_scores' float32 values (the
+    float64 sum rounded once), returned as float32.  W: slim_columns' triple; path as slim_scores."""
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    w_ptr, w_row, w_val = W
+    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
+        users, U, targets, exclude, return_scores, return_eligible, validate, w_ptr.device, torch.float32)
+    check(lib.daisy_slim_full_rank_positions(rp, cp, vp, U, int(item_num), _ptr(w_ptr, torch.int64, "w_ptr"),
+                                             _ptr(w_row, torch.int32, "w_row"), _ptr(w_val, torch.float32, "w_val"),
+                                             _ptr(users, torch.int64, "users"), n, *ptrs,
+                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
+                                             _ptr(scores, torch.float32, "scores"), _ptr(eligible, torch.int32, "eligible"),
+                                             N.SLIM_PATHS[path], _stream()))
+    return _rank_positions_out(out_indptr, pos, scores, eligible)
+
+
+def knn_full_rank_positions(L, R, inner, n_cols, users, targets, exclude=None, return_scores=False, return_eligible=False,
+                            validate=True, path="auto"):
+    """ease_full_rank_positions for ItemKNN / UserKNN (daisy_knn_full_rank_positions): the float64 scores L[users] R of
+    knn_rank.  L: a CSR triple [U, inner]; R: a by-column triple [inner, n_cols]; path as knn_rank."""
+    lp, lc, lv, n_rows = _slim_csr_ptrs(L)
+    rp, rc, rv, nc = _slim_csr_ptrs(R)
+    if nc != int(n_cols):
+        raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
+    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
+        users, n_rows, targets, exclude, return_scores, return_eligible, validate, L[0].device, torch.float64)
+    check(lib.daisy_knn_full_rank_positions(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols),
+                                            _ptr(users, torch.int64, "users"), n, *ptrs,
+                                            _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
+                                            _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
+                                            N.SLIM_PATHS[path], _stream()))
+    return _rank_positions_out(out_indptr, pos, scores, eligible)
+
+
+def psvd_full_rank_positions(user_vec, item_vec, users, targets, exclude=None, return_scores=False, return_eligible=False,
+                             validate=True):
+    """ease_full_rank_positions for PureSVD (daisy_psvd_full_rank_positions): the float64 scores <user_vec[u], item_vec[i]>
+    of psvd_rank."""
+    up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
+    U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
+    if item_vec.shape[1] != k:
+        raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
+    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
+        users, U, targets, exclude, return_scores, return_eligible, validate, user_vec.device, torch.float64)
+    check(lib.daisy_psvd_full_rank_positions(up, ip, U, I, k, _ptr(users, torch.int64, "users"), n, *ptrs,
+                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
+                                             _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
+                                             _stream()))
+    return _rank_positions_out(out_indptr, pos, scores, eligible)
+
+
 # ---- masked top-k over rows of fp32 scores (csrc/rank_rows.hip; DESIGN.md §26) --------------------------------------------
 RANK_ROWS_TOPK_CAP = 128      # kRrTopkCap (csrc/rank_rows.hip): the candidate buffer of a row lives in LDS
 RANK_ROWS_STEP = 1024         # kRrStep: items a workgroup takes per step (the tests' edge sizes)
@@ -2183,6 +2313,49 @@ def rank_rows_f32(scores, topk, row_users=None, exclude=None, return_scores=Fals
                                       _ptr(indptr, torch.int64, "exclude indptr"), _ptr(items, torch.int32, "exclude items"),
                                       topk, _ptr(ids, torch.int64, "ids"), _ptr(sc, torch.float32, "scores"), _stream()))
     return (ids, sc) if return_scores else ids
+
+
+def rank_rows_positions_f32(scores, row_users, targets, exclude=None, return_scores=False, return_eligible=False,
+                            validate=True, out=None):
+    """The exact 0-based rank of every held-out item in its row of a score matrix, in one launch
+    (daisy_rank_rows_positions_f32): scores as in rank_rows_f32; row_users int64 [m] names, for score row r,
+    the row of `targets` = (indptr int64 [U + 1], items int32 ascending per row) and of `exclude` (the same form, or None).
+    The position of target t is the number of items of the row outside the exclusion that come before it in rank_rows_f32's
+    order - score descending, a NaN first, -0.0 equal to +0.0, equal scores by ascending id - so rank_rows_f32's ids[r,
+    pos] == t wherever pos < topk, without a cap.  -> ops.full_rank_positions' tuple (out_indptr int64 [m + 1], positions
+    int32 [T][, scores float32 [T]][, eligible int32 [m]]): -1 (score -inf) for a target outside [0, I) or excluded; a
+    score is the row's own stored value (the same bits); eligible = I minus the distinct excluded ids in [0, I).
+    validate: ops.full_rank_positions' checks on row_users, exclude and targets; False skips them.  out: (out_indptr int64
+    [m + 1], positions, scores or None, eligible int32 [m] or None) to write into instead of new tensors - out_indptr
+    holds the rows' offsets into positions (and scores), which may be longer than these rows' share: a caller that walks a
+    large request in chunks of score rows passes slices of one out_indptr and one eligible, and the whole positions."""
+    ptr, pitch = _rows(scores, "scores")
+    m, I = int(scores.shape[0]), int(scores.shape[1])
+    if m > 1 and scores.stride(0) < I:
+        raise ValueError(f"scores: rows overlap (stride {scores.stride(0)} below {I} columns)")
+    if row_users is None:
+        raise ValueError("rank_rows_positions_f32: row_users is required (the CSR row of every score row)")
+    dev = scores.device
+    row_users = torch.as_tensor(row_users).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    if row_users.numel() != m:
+        raise ValueError(f"row_users: {row_users.numel()} entries for {m} score rows")
+    U = int(targets[0].numel()) - 1
+    if out is None:
+        _, _, T, ptrs, out_indptr, pos, sc, eligible, _keep = _rank_positions_args(
+            row_users, U, targets, exclude, return_scores, return_eligible, validate, dev, torch.float32)
+    else:
+        out_indptr, pos, sc, eligible = out
+        if out_indptr.numel() != m + 1 or (sc is not None and sc.numel() != pos.numel()) or \
+                (eligible is not None and eligible.numel() != m):
+            raise ValueError(f"out: expected out_indptr [{m + 1}], scores as long as positions and eligible [{m}]")
+        _, ptrs, _keep = _rank_positions_request(row_users, U, targets, exclude, validate, dev)
+        T = int(pos.numel())
+    if m:
+        check(lib.daisy_rank_rows_positions_f32(ptr, m, I, pitch, _ptr(row_users, torch.int64, "row_users"), *ptrs,
+                                                _ptr(out_indptr, torch.int64, "out_indptr"), T,
+                                                _ptr(pos, torch.int32, "positions"), _ptr(sc, torch.float32, "scores"),
+                                                _ptr(eligible, torch.int32, "eligible"), _stream()))
+    return _rank_positions_out(out_indptr, pos, sc, eligible)
 
 
 # ---- MostPop and the ranking KPIs (csrc/pop.hip, csrc/metrics.hip; DESIGN.md §20) ----------------------------------------

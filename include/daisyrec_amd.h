@@ -1197,6 +1197,52 @@ int daisy_psvd_full_rank_users(const double *user_vec, const double *item_vec, i
                                int32_t topk, int64_t *out_ids, double *out_scores, daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Exact ranks of held-out items over all items on fp64 scores: EASE, SLiM, ItemKNN / UserKNN, PureSVD
+ * (csrc/rank_positions_f64.hip, csrc/rank_f64_positions.h, csrc/rank_count.h; additive to ABI 8)
+ * ---------------------------------------------------------------------- */
+/* The model arguments, users [n], the exclusion CSR and SLiM's / KNN's path are the *_full_rank_users sibling's; the scores
+ * come from the same scorer and device function, so they are that entry's bits.  tgt_indptr int64 [user_num + 1] /
+ * tgt_items int32: the TARGET CSR over all users (daisy_build_user_csr's).  out_indptr int64 [n + 1]: the prefix sum of the
+ * target-row lengths of users[0 .. n), built by the caller; n_targets = out_indptr[n].  Order: the key of score + 0.0
+ * descending (SLiM: after its rounding to fp32), equal keys by ascending item id, a NaN is never ranked.  With E_u the
+ * items of [0, item_num) outside u's exclusion row whose score is a number, request b's target number r (row order) gets
+ *   out_pos[out_indptr[b] + r]   int32: #{ j in E_u : j comes before t } - its 0-based rank; -1 for a target outside
+ *                                [0, item_num) (it is range-checked before it indexes anything), inside the exclusion row
+ *                                or with a NaN score
+ *   out_scores[...]              fp64 (fp32 for SLiM) or NULL: the target's score; -inf for the first two cases of pos = -1,
+ *                                the computed NaN for the third
+ *   out_eligible[b]              int32 or NULL: |E_u|
+ * so that with the same arguments the sibling's ids[b][pos] == t for every target with 0 <= pos < topk, and no other
+ * target appears in row b.  One launch of one 256-thread workgroup per request, which takes the target row in blocks of
+ * 512 (sorted in LDS; every item looks up its bucket by binary search) and scores the items once per block: no cap on the
+ * row length, no workspace, nothing of size n * item_num.  A request without targets streams only when out_eligible is
+ * given.  The counts are integer LDS atomics: two runs give the same bits.  Row contents of the exclusion are only
+ * compared, writes to out_pos / out_scores are bounded by n_targets; user ids, the indptr arrays and out_indptr are the
+ * caller's to validate.  Every argument is checked before the first HIP call; n == 0 returns DAISY_OK without a launch. */
+int daisy_ease_full_rank_positions(const int64_t *row_ptr, const int32_t *col, const float *val, const double *W,
+                                   int64_t user_num, int64_t item_num, const int64_t *users, int64_t n,
+                                   const int64_t *excl_indptr, const int32_t *excl_items, const int64_t *tgt_indptr,
+                                   const int32_t *tgt_items, const int64_t *out_indptr, int64_t n_targets, int32_t *out_pos,
+                                   double *out_scores, int32_t *out_eligible, daisy_stream_t stream);
+int daisy_slim_full_rank_positions(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t user_num,
+                                   int64_t item_num, const int64_t *w_ptr, const int32_t *w_row, const float *w_val,
+                                   const int64_t *users, int64_t n, const int64_t *excl_indptr, const int32_t *excl_items,
+                                   const int64_t *tgt_indptr, const int32_t *tgt_items, const int64_t *out_indptr,
+                                   int64_t n_targets, int32_t *out_pos, float *out_scores, int32_t *out_eligible, int32_t path,
+                                   daisy_stream_t stream);
+int daisy_knn_full_rank_positions(const int64_t *l_ptr, const int32_t *l_col, const float *l_val, int64_t n_rows, int64_t inner,
+                                  const int64_t *r_ptr, const int32_t *r_row, const float *r_val, int64_t n_cols,
+                                  const int64_t *users, int64_t n, const int64_t *excl_indptr, const int32_t *excl_items,
+                                  const int64_t *tgt_indptr, const int32_t *tgt_items, const int64_t *out_indptr,
+                                  int64_t n_targets, int32_t *out_pos, double *out_scores, int32_t *out_eligible, int32_t path,
+                                  daisy_stream_t stream);
+int daisy_psvd_full_rank_positions(const double *user_vec, const double *item_vec, int64_t user_num, int64_t item_num, int32_t k,
+                                   const int64_t *users, int64_t n, const int64_t *excl_indptr, const int32_t *excl_items,
+                                   const int64_t *tgt_indptr, const int32_t *tgt_items, const int64_t *out_indptr,
+                                   int64_t n_targets, int32_t *out_pos, double *out_scores, int32_t *out_eligible,
+                                   daisy_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Masked top-k over rows of fp32 scores (csrc/rank_rows.hip; additive to ABI 8): the selector of
  * full_rank_users for NeuMF, NFM and Multi-VAE, whose scores come out of kernels of their own
  * ---------------------------------------------------------------------- */
@@ -1216,6 +1262,25 @@ int daisy_psvd_full_rank_users(const double *user_vec, const double *item_vec, i
 int daisy_rank_rows_f32(const float *scores, int64_t m, int64_t item_num, int64_t pitch, const int64_t *row_users,
                         const int64_t *excl_indptr, const int32_t *excl_items, int32_t topk, int64_t *out_ids,
                         float *out_scores, daisy_stream_t stream);
+/* Exact ranks of held-out items over rows of fp32 scores (csrc/rank_rows_positions.hip; additive to ABI 8).
+ * scores, m, item_num, pitch and the exclusion CSR are daisy_rank_rows_f32's; row_users int64 [m] is required: row_users[r]
+ * names the CSR row of both the exclusion and the targets of score row r.  tgt_indptr / tgt_items, out_indptr int64
+ * [m + 1] (the prefix sum of the rows' target-row lengths) and n_targets are as in daisy_ease_full_rank_positions.  With
+ * word(j) = (key of scores[r][j] << 32) | (0xFFFFFFFF - j) - score descending, a NaN first, -0.0 equal to +0.0, equal
+ * scores by ascending id - target t of row r gets
+ *   out_pos      int32: #{ j < item_num not excluded : word(j) > word(t) }; -1 for a target outside [0, item_num) (range-
+ *                checked before it indexes anything) or excluded
+ *   out_scores   fp32 or NULL: the row's own stored value with its bits; -inf where pos = -1
+ *   out_eligible int32 [m] or NULL: item_num - (distinct excluded ids in [0, item_num))
+ * so that with the same arguments daisy_rank_rows_f32's ids[r][pos] == t wherever pos < topk.  One launch of one
+ * 256-thread workgroup per row; float4 loads when scores is 16-byte aligned and pitch % 4 == 0, element loads otherwise; no
+ * load reaches past item_num values of a row.  Target rows longer than 512 re-read the score row once per block of 512.
+ * No workspace, integer LDS atomics only: two runs give the same bits.  Writes are bounded by n_targets.  Every argument
+ * is checked before the first HIP call; m == 0 returns DAISY_OK without a launch. */
+int daisy_rank_rows_positions_f32(const float *scores, int64_t m, int64_t item_num, int64_t pitch, const int64_t *row_users,
+                                  const int64_t *excl_indptr, const int32_t *excl_items, const int64_t *tgt_indptr,
+                                  const int32_t *tgt_items, const int64_t *out_indptr, int64_t n_targets, int32_t *out_pos,
+                                  float *out_scores, int32_t *out_eligible, daisy_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * MostPop(daisy/model/PopRecommender.py) and the ranking KPIs (daisy/utils/metrics.py): csrc/pop.hip, csrc/metrics.hip;
