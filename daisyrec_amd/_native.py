@@ -103,6 +103,7 @@ SLIM_LDS_ITEMS, SLIM_MAX_TOPK = 9984, 1024
 SLIM_PATHS = {"auto": 0, "lds": 1, "global": 2}
 PSVD_MAX_C, PSVD_CONVERGED, PSVD_NOT_CONVERGED = 256, 0, 1
 EASE_BLOCK = 64
+IALS_MAX_D = 128
 KNN_MAX_K = 1024
 KNN_CENTER = {"none": 0, "row": 1, "col": 2, "binary": 3}
 KNN_MODES = {"cosine": 0, "asymmetric": 1, "tanimoto": 2, "dice": 3, "tversky": 4, "plain": 5}
@@ -265,6 +266,13 @@ SIGNATURES = {
     "daisy_ease_potri": (C.c_int, [_p, _i64, _p, _p, _p, _sz, _p]),
     "daisy_ease_weights": (C.c_int, [_p, _i64, _p, _p, _sz, _p]),
     "daisy_ease_rank": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "daisy_ials_gram_workspace_bytes": (_sz, [_i64, _i32]),
+    "daisy_ials_gram": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
+    "daisy_ials_half_sweep": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _i32, _p, C.c_double, C.c_double, _p, _i64,
+                                        _p, _p, _p, _p]),
+    "daisy_ials_objective_workspace_bytes": (_sz, [_i64]),
+    "daisy_ials_objective": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, C.c_double, C.c_double, _p,
+                                       _p, _sz, _p]),
     "daisy_knn_row_means": (C.c_int, [_p, _p, _i64, _p, _p]),
     "daisy_knn_center": (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p]),
     "daisy_knn_diag": (C.c_int, [_p, _i64, _i32, _p, _p]),

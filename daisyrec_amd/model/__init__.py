@@ -10,5 +10,6 @@ from .VAECFRecommender import VAECF  # noqa: F401
 from .SLiMRecommender import SLiM  # noqa: F401
 from .PureSVDRecommender import PureSVD  # noqa: F401
 from .EASERecommender import EASE  # noqa: F401
+from .IALSRecommender import IALS  # noqa: F401
 from .KNNCFRecommender import ItemKNNCF, UserKNNCF  # noqa: F401
 from .PopRecommender import MostPop  # noqa: F401

@@ -1890,6 +1890,94 @@ def ease_rank(csr, W, users, items=None, topk=0):
     return scores, ids
 
 
+# ---- iALS (csrc/ials.hip; IALSRecommender.py) -------------------------------------------------------------------
+def _ials_table(t, name):
+    """(pointer, rows, row pitch, d) of an fp32 factor table: _rows' layouts, d within the kernels' limit."""
+    p, ld = _rows(t, name)
+    d = int(t.shape[1])
+    if d < 1 or d > N.IALS_MAX_D:
+        raise ValueError(f"{name}: d={d} factors outside [1, {N.IALS_MAX_D}]")
+    return p, int(t.shape[0]), ld, d
+
+
+def _ials_csr(csr, n_other, validate):
+    """_slim_csr_ptrs plus the entry count; validate: IndexError for a column id outside [0, n_other) and ValueError for
+    a row_ptr that does not rise from 0 to len(col) (one read-back)."""
+    row_ptr, col, val = csr
+    nnz = int(col.numel())
+    if val.numel() != nnz:
+        raise ValueError(f"csr: {nnz} column ids but {val.numel()} values")
+    if validate:
+        ok = (row_ptr[1:] >= row_ptr[:-1]).all() & (row_ptr[0] == 0) & (row_ptr[-1] == nnz)
+        lo = col.min() if nnz else torch.zeros((), dtype=torch.int32, device=col.device)
+        hi = col.max() if nnz else lo
+        ok, lo, hi = (int(x) for x in torch.stack([ok.to(torch.int64), lo.to(torch.int64), hi.to(torch.int64)]).tolist())
+        if not ok:
+            raise ValueError(f"csr: row_ptr must rise from 0 to len(col) = {nnz}")
+        if lo < 0 or hi >= n_other:
+            raise IndexError(f"index {hi if hi >= n_other else lo} is out of bounds for the table with {n_other} rows")
+    return _slim_csr_ptrs(csr) + (nnz,)
+
+
+def ials_gram(Y):
+    """G [d, d] = Y^T Y, float64, of a float32 table Y [n, d] whose rows may sit on a wider pitch (daisy_ials_gram):
+    blocks of rows on the fp64 MFMA, their partial products added in block order; bitwise symmetric."""
+    yp, n, ld, d = _ials_table(Y, "Y")
+    ws = _ws(lib.daisy_ials_gram_workspace_bytes(n, d), Y.device)
+    G = torch.empty(d, d, dtype=torch.float64, device=Y.device)
+    check(lib.daisy_ials_gram(yp, n, ld, d, _ptr(G, torch.float64, "G"), _ptr(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return G
+
+
+def ials_half_sweep(csr, Y, alpha, reg, G=None, out=None, dump=False, validate=True):
+    """One half-sweep of alternating least squares (daisy_ials_half_sweep) -> (X float32 [rows, d], info int32 [1]):
+    X[u] = (G + reg I + sum_i alpha r_ui y_i y_i^T)^-1 sum_i (1 + alpha r_ui) y_i over row u of csr (slim_csr's triple,
+    entries in stored order), solved in fp64 by a Cholesky factorisation and rounded once.  G: ials_gram(Y), computed
+    when None.  out: the table to write (rows may sit on a wider pitch).  An empty row gives zeros; info is 0, or
+    1 + the smallest row whose system is not positive definite (its output is NaN).  dump=True: (X, info, A float64
+    [rows, d, d], b float64 [rows, d]), the systems before factoring.  validate: IndexError for a column id outside
+    [0, len(Y)) (one read-back); False trusts the ids - the kernel skips an entry whose id is out of range."""
+    yp, n_other, ldy, d = _ials_table(Y, "Y")
+    rp, cp, vp, rows, nnz = _ials_csr(csr, n_other, validate)
+    dev = Y.device
+    if G is None:
+        G = ials_gram(Y)
+    if G.dim() != 2 or tuple(G.shape) != (d, d):
+        raise ValueError(f"G: expected [{d}, {d}], got {tuple(G.shape)}")
+    if out is None:
+        out = torch.empty(rows, d, dtype=torch.float32, device=dev)
+    xp, xrows, ldx, xd = _ials_table(out, "out")
+    if xrows != rows or xd != d:
+        raise ValueError(f"out: expected [{rows}, {d}], got {tuple(out.shape)}")
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    A = torch.empty(rows, d, d, dtype=torch.float64, device=dev) if dump else None
+    b = torch.empty(rows, d, dtype=torch.float64, device=dev) if dump else None
+    check(lib.daisy_ials_half_sweep(rp, cp, vp, rows, nnz, n_other, yp, ldy, d, _ptr(G, torch.float64, "G"), float(alpha),
+                                    float(reg), xp, ldx, _ptr(info, torch.int32, "info"), _ptr(A, torch.float64, "A"),
+                                    _ptr(b, torch.float64, "b"), _stream()))
+    return (out, info, A, b) if dump else (out, info)
+
+
+def ials_objective(csr, X, Y, alpha, reg, G=None, validate=False):
+    """The iALS objective (daisy_ials_objective) as a 0-dim float64 device tensor: sum over ALL cells of
+    c_ui (p_ui - <x_u, y_i>)^2 with p = 1, c = 1 + alpha r on the entries of csr and p = 0, c = 1 elsewhere, plus
+    reg (|X|^2 + |Y|^2) - by the Gram trick (x^T G x per row and a correction per entry), one partial per row added in
+    a fixed order.  G: ials_gram(Y), computed when None."""
+    yp, n_other, ldy, d = _ials_table(Y, "Y")
+    xp, xrows, ldx, xd = _ials_table(X, "X")
+    rp, cp, vp, rows, nnz = _ials_csr(csr, n_other, validate)
+    if xrows != rows or xd != d:
+        raise ValueError(f"X: expected [{rows}, {d}], got {tuple(X.shape)}")
+    if G is None:
+        G = ials_gram(Y)
+    out = torch.empty((), dtype=torch.float64, device=Y.device)
+    ws = _ws(lib.daisy_ials_objective_workspace_bytes(rows), Y.device)
+    check(lib.daisy_ials_objective(rp, cp, vp, rows, nnz, n_other, xp, ldx, yp, ldy, d, _ptr(G, torch.float64, "G"),
+                                   float(alpha), float(reg), C.c_void_p(out.data_ptr()), _ptr(ws, torch.uint8, "ws"),
+                                   ws.numel(), _stream()))
+    return out
+
+
 # ---- ItemKNN / UserKNN (csrc/knn.hip; KNNCFRecommender.py; DESIGN.md §19) ------------------------------------------------------
 KNN_SIMILARITIES = ("cosine", "pearson", "adjusted", "asymmetric", "jaccard", "tanimoto", "dice", "tversky")
 _KNN_BINARY = {"jaccard": "tanimoto", "tanimoto": "tanimoto", "dice": "dice", "tversky": "tversky"}

@@ -1435,6 +1435,39 @@ int daisy_history_csr(const int32_t *row, const int32_t *col, const double *val,
 int daisy_history_first_seen(const int32_t *ids, int64_t n, int64_t id_num, int64_t *out, int64_t *count_host,
                              daisy_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * iALS / WRMF (Hu, Koren, Volinsky 2008; no counterpart in the reference): weighted matrix factorisation of implicit
+ * feedback by alternating least squares (csrc/ials.hip).  The tables are fp32 [n, d] with an explicit row
+ * pitch (ld >= d, in elements), 1 <= d <= DAISY_IALS_MAX_D; the sparse operand is daisy_slim_gram's CSR (row_ptr int64
+ * [rows + 1], col int32, val fp32 - nnz entries each).  All arithmetic between the fp32 operands and the fp32 result is
+ * fp64 in a fixed order: no floating-point atomics, two calls give the same bits.
+ * ---------------------------------------------------------------------- */
+#define DAISY_IALS_MAX_D 128
+/* G fp64 [d, d] = Y^T Y on the fp64 MFMA: blocks of rows write partial products, a second pass adds them in block order.
+ * G is bitwise symmetric.  n >= 1. */
+size_t daisy_ials_gram_workspace_bytes(int64_t n, int32_t d);
+int daisy_ials_gram(const float *Y, int64_t n, int64_t ld, int32_t d, double *G, void *workspace, size_t workspace_bytes,
+                    daisy_stream_t stream);
+/* One half-sweep: for every CSR row u, X[u] = fp32(A_u^-1 b_u) with A_u = G + reg I + sum_i alpha r_ui y_i y_i^T and
+ * b_u = sum_i (1 + alpha r_ui) y_i over the row's entries in stored order, G = Y^T Y of the other side's table Y
+ * [n_other, d] (daisy_ials_gram).  One workgroup per row: the rank-one updates on the fp64 MFMA, a Cholesky factorisation
+ * and both triangular solves in LDS.  An empty row gives exact zeros.  A column id outside [0, n_other) contributes
+ * nothing (callers validate).  A pivot that is not positive and finite makes the row's output NaN and records
+ * 1 + the row index in *info (int32, device) by an integer atomicMin: the smallest such row, 0 when there is none.
+ * dump_A fp64 [rows, d, d] (full symmetric) and dump_b fp64 [rows, d], each or both NULL, receive the systems before
+ * they are factored.  reg = 0 is allowed. */
+int daisy_ials_half_sweep(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t rows, int64_t nnz,
+                          int64_t n_other, const float *Y, int64_t ldy, int32_t d, const double *G, double alpha, double reg,
+                          float *X, int64_t ldx, int32_t *info, double *dump_A, double *dump_b, daisy_stream_t stream);
+/* *out (fp64, device) = sum_u [ x_u^T G x_u + sum_{i in row u} ((1 + alpha r_ui)(1 - s_ui)^2 - s_ui^2) ]
+ *                       + reg (|X|^2 + trace G), s_ui = <x_u, y_i>: the weighted squared error over ALL cells plus the
+ * regulariser, without a pass over the cells.  One partial per row (the workspace), added in a fixed order. */
+size_t daisy_ials_objective_workspace_bytes(int64_t rows);
+int daisy_ials_objective(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t rows, int64_t nnz,
+                         int64_t n_other, const float *X, int64_t ldx, const float *Y, int64_t ldy, int32_t d, const double *G,
+                         double alpha, double reg, double *out, void *workspace, size_t workspace_bytes,
+                         daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
