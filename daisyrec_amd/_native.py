@@ -105,6 +105,7 @@ PSVD_MAX_C, PSVD_CONVERGED, PSVD_NOT_CONVERGED = 256, 0, 1
 EASE_BLOCK = 64
 IALS_MAX_D = 128
 KNN_MAX_K = 1024
+WALK2_LDS_COLS = 32768
 KNN_CENTER = {"none": 0, "row": 1, "col": 2, "binary": 3}
 KNN_MODES = {"cosine": 0, "asymmetric": 1, "tanimoto": 2, "dice": 3, "tversky": 4, "plain": 5}
 # daisy_ranking_kpis: bit (1 << id) of the metrics mask; the first KPI_PER_USER have a value per list
@@ -280,6 +281,9 @@ SIGNATURES = {
     "daisy_knn_rank": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _i32, _p]),
     "daisy_knn_fit_bytes": (_sz, [_i64, _i64, _i32]),
     "daisy_knn_fits": (C.c_int, [_i64, _i64, _i32, _sz]),
+    "daisy_walk2_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "daisy_walk2_topk": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p,
+                                   _sz, _p]),
     "daisy_rank_f64_users_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "daisy_ease_full_rank_users": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _p, _p, _p]),
     "daisy_slim_full_rank_users": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p]),

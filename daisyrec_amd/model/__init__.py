@@ -12,4 +12,5 @@ from .PureSVDRecommender import PureSVD  # noqa: F401
 from .EASERecommender import EASE  # noqa: F401
 from .IALSRecommender import IALS  # noqa: F401
 from .KNNCFRecommender import ItemKNNCF, UserKNNCF  # noqa: F401
+from .RP3betaRecommender import P3alpha, RP3beta  # noqa: F401
 from .PopRecommender import MostPop  # noqa: F401

@@ -2124,8 +2124,65 @@ def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
     return scores, ids
 
 
+# ---- two-hop walk with a per-row top-K (csrc/walk2.hip; RP3betaRecommender.py) ---------------------------
+def _walk2_check_sorted(csr, n_cols, name):
+    """ValueError unless csr is a CSR whose columns lie in [0, n_cols), ascending and distinct within a row (one read-back)."""
+    row_ptr, col, _ = csr
+    nnz = int(col.numel())
+    ok = (row_ptr[1:] >= row_ptr[:-1]).all() & (row_ptr[0] == 0) & (row_ptr[-1] == nnz)
+    in_range = rising = torch.ones((), dtype=torch.bool, device=col.device)
+    if nnz:
+        c = col.to(torch.int64)
+        in_range = (c.min() >= 0) & (c.max() < int(n_cols))
+        first = torch.zeros(nnz + 1, dtype=torch.bool, device=col.device)
+        first[row_ptr.clamp(0, nnz)] = True                        # the first entry of every row: nothing to compare with
+        rising = ((c[1:] > c[:-1]) | first[1:nnz]).all()
+    ok, in_range, rising = (bool(x) for x in torch.stack([ok, in_range, rising]).tolist())
+    if not ok:
+        raise ValueError(f"{name}: row_ptr must rise from 0 to len(col) = {nnz}")
+    if not in_range:
+        raise ValueError(f"{name}: a column id lies outside [0, {int(n_cols)})")
+    if not rising:
+        raise ValueError(f"{name}: the columns of a row must be ascending and distinct")
+
+
+def walk2_topk(A, B, n_cols, K, col_scale=None, zero_diagonal=True, normalize=False, path="auto", validate=True, groups=0,
+               workspace=None):
+    """The K largest strictly positive entries of every row of (A B) diag(col_scale) without the dense product
+    (daisy_walk2_topk) -> (count int32 [n_rows], cols int32 [n_rows, K], vals float32 [n_rows, K]) in knn_select's
+    fixed-pitch form, ascending column within a row, unused slots (-1, 0).  A: a CSR triple [n_rows, inner]; B: a CSR triple
+    [inner, n_cols] (slim_csr's layout, columns ascending and distinct within a row).  Row i: the products A[i, u] B[u, j]
+    rounded to float32 and added in float32 over u in stored order, times col_scale[j] (float32 [n_cols]; None: no
+    multiply); zero_diagonal: entry (i, i) is dropped; ties at the boundary go to the lower column; normalize: the kept
+    values divided by their float32 sum.  path: 'auto' | 'lds' | 'global', bit-equal; groups: the workgroups of the launch
+    (0: chosen from the shape), bit-equal for any count.  validate: ValueError unless B's columns are ascending, distinct and
+    in range and A's lie in [0, inner) (one read-back each).  workspace: a uint8 device tensor to use instead of a fresh
+    one."""
+    if path not in N.SLIM_PATHS:
+        raise ValueError(f"walk2_topk: path={path!r}: expected 'auto', 'lds' or 'global'")
+    inner, nc, k = B[0].numel() - 1, int(n_cols), int(K)
+    if validate:
+        _walk2_check_sorted(B, nc, "B")
+        _ials_csr(A, inner, True)
+    ap, ac, av, n_rows = _slim_csr_ptrs(A)
+    bp, bc, bv, _ = _slim_csr_ptrs(B)
+    dev = A[0].device
+    if col_scale is not None and col_scale.numel() != nc:
+        raise ValueError(f"col_scale: expected {nc} values, got {col_scale.numel()}")
+    p = N.SLIM_PATHS[path]
+    count = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    cols = torch.empty(n_rows, max(k, 0), dtype=torch.int32, device=dev)
+    vals = torch.empty(n_rows, max(k, 0), dtype=torch.float32, device=dev)
+    ws = _ws(lib.daisy_walk2_workspace_bytes(n_rows, nc, p, int(groups)), dev) if workspace is None else workspace
+    check(lib.daisy_walk2_topk(ap, ac, av, n_rows, inner, bp, bc, bv, nc, _ptr(col_scale, torch.float32, "col_scale"),
+                               int(bool(zero_diagonal)), int(bool(normalize)), k, _ptr(count, torch.int32, "count"),
+                               _ptr(cols, torch.int32, "cols"), _ptr(vals, torch.float32, "vals"), p, int(groups),
+                               _ptr(ws, torch.uint8, "workspace"), ws.numel(), _stream()))
+    return count, cols, vals
+
+
 # ---- full ranking of many users on fp64 scores (csrc/rank_full_f64.hip; DESIGN.md §25) ------------------------------------
-RANK_F64_TOPK_CAP = 128       # kRfTopkCap (csrc/rank_f64_users.h): the candidate buffer of a user lives in LDS
+RANK_F64_TOPK_CAP = 128      # kRfTopkCap (csrc/rank_f64_users.h): the candidate buffer of a user lives in LDS
 
 
 def _rank_f64_users_args(users, user_num, topk, exclude, return_scores, validate, device, score_dtype):

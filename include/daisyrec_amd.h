@@ -1468,6 +1468,32 @@ int daisy_ials_objective(const int64_t *row_ptr, const int32_t *col, const float
                          double alpha, double reg, double *out, void *workspace, size_t workspace_bytes,
                          daisy_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Two-hop walk with a per-row top-K (csrc/walk2.hip; additive to ABI 8): the primitive of RP3beta and
+ * P3alpha (Cooper et al. 2014, Paudel et al. 2016; no counterpart in the reference).  A is a CSR [n_rows, inner], B a CSR
+ * [inner, n_cols], both of daisy_slim_gram's layout (row_ptr int64, col int32, val fp32); the columns of every row of B
+ * are ascending and distinct (callers validate).  For every row i of A:
+ *   acc[j] = sum over the stored entries u of row i, in stored order, of A[i, u] * B[u, j]: every product rounded to fp32,
+ *            then added in fp32 (no fused multiply-add);
+ *   w[j]   = acc[j] * col_scale[j], one rounded fp32 multiply (col_scale == NULL: w = acc); zero_diagonal: w[i] = 0;
+ *   the K largest strictly positive w are kept, ties at the boundary to the LOWER j; zero, negative and NaN never;
+ *   normalize: the kept values are divided by their fp32 sum, taken in ascending j.
+ * Outputs in daisy_knn_select's fixed-pitch form: count int32 [n_rows]; cols int32 / vals fp32 [n_rows, K], ascending j,
+ * unused slots (-1, 0).  1 <= K <= DAISY_KNN_MAX_K (K >= n_cols is allowed).  A column id of A outside [0, inner) or of B
+ * outside [0, n_cols) contributes nothing.
+ * One workgroup per source row at a time, rows handed out by an integer counter; the dense accumulator over n_cols lives in
+ * LDS (path LDS; AUTO up to DAISY_WALK2_LDS_COLS columns) or in a slab of the workspace per workgroup (path GLOBAL;
+ * DAISY_SLIM_PATH_*).  n_groups: the workgroups of the launch (0: chosen from the shape).  No floating-point atomics:
+ * every acc[j] receives its terms in ascending u whatever the path and n_groups - two runs, the two paths and any two
+ * n_groups give the same bits.  The work is the number of two-hop paths, the memory n_rows * K. */
+#define DAISY_WALK2_LDS_COLS 32768
+/* bytes of workspace daisy_walk2_topk needs (the row counter, and the slabs of path GLOBAL); 0 on bad arguments */
+size_t daisy_walk2_workspace_bytes(int64_t n_rows, int64_t n_cols, int32_t path, int32_t n_groups);
+int daisy_walk2_topk(const int64_t *a_ptr, const int32_t *a_col, const float *a_val, int64_t n_rows, int64_t inner,
+                     const int64_t *b_ptr, const int32_t *b_col, const float *b_val, int64_t n_cols, const float *col_scale,
+                     int32_t zero_diagonal, int32_t normalize, int32_t K, int32_t *count, int32_t *cols, float *vals,
+                     int32_t path, int32_t n_groups, void *workspace, size_t workspace_bytes, daisy_stream_t stream);
+
 /* micro-benchmarks of the memory system used to place the kernels on the
  * roofline (tools/membench.py); not part of the reference surface. */
 int daisy_membench(int32_t what, float *table, int64_t rows, int32_t d, const int32_t *idx,
