@@ -17,13 +17,16 @@ are ranked in stable order where the reference's argsort leaves them unspecified
 from __future__ import annotations
 
 import numpy as np
-import torch
 
 from .. import ops
-from .AbstractRecommender import GeneralRecommender
+from ._frame import FrameRecommender
 
 
-class EASE(GeneralRecommender):
+class EASE(FrameRecommender):
+    _name = "EASE"
+    _rank_op = staticmethod(ops.ease_rank)
+    _users_op = staticmethod(ops.ease_full_rank_users)      # (no _positions_op yet: ops.ease_full_rank_positions is there)
+
     def __init__(self, config):
         """Config keys as in EASERecommender.py:17-28 (ease.yaml + basic.yaml)."""
         super().__init__(config)
@@ -46,31 +49,14 @@ class EASE(GeneralRecommender):
         self.fit_info = None
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _frame_columns(self, df):
-        """EASERecommender.py:31-33: the configured columns, range-checked."""
-        cols = []
-        for name, hi, what in ((self.uid_name, self.user_num, "user"), (self.iid_name, self.item_num, "item")):
-            ids = np.asarray(df[name])
-            if ids.size and not np.issubdtype(ids.dtype, np.integer):
-                if not np.all(ids == np.floor(ids)):
-                    raise ValueError(f"EASE.fit: column '{name}' holds non-integer ids")
-            ids = ids.astype(np.int64)
-            if ids.size and (ids.min() < 0 or ids.max() >= hi):
-                bad = ids.max() if ids.max() >= hi else ids.min()
-                raise ValueError(f"EASE.fit: {what} id {int(bad)} outside [0, {hi})")
-            cols.append(ids)
-        ratings = np.asarray(df[self.inter_name], dtype=np.float64)
-        if not np.all(np.isfinite(ratings)):
-            raise ValueError(f"EASE.fit: column '{self.inter_name}' holds a value that is not finite")
-        return cols[0], cols[1], ratings
+    @property
+    def _columns(self):
+        """EASERecommender.py:31-33: the configured columns"""
+        return self.uid_name, self.iid_name, self.inter_name
 
     def fit(self, train_set):
         """EASERecommender.py:30-47: Gram matrix, the fp64 inverse, B = -P / diag(P); B and X stay on the device."""
-        users, items, ratings = self._frame_columns(train_set)
-        self._require_device()
-        dev = torch.device(self.device)
-        csr = ops.slim_csr(torch.from_numpy(users).to(dev), torch.from_numpy(items).to(dev),
-                           torch.from_numpy(ratings).to(dev), self.user_num, self.item_num)
+        csr, _ = self._frame_csr(train_set)
         B, info = ops.ease_fit(csr, self.item_num, self.reg_weight)
         info = int(info.cpu().item())
         self.fit_info = {"info": info, "bytes_held": B.numel() * 8 + sum(t.numel() * t.element_size() for t in csr),
@@ -80,10 +66,8 @@ class EASE(GeneralRecommender):
                                f"column {info - 1} is not positive")
         self._csr, self._B = csr, B
 
-    def _fitted(self):
-        self._require_device()
-        if self._B is None:
-            raise RuntimeError("EASE: fit(train_set) has not been called")
+    def _has_fit(self):
+        return self._B is not None
 
     # -- the reference's attributes, built on demand -------------------------------------------------------------------
     @property
@@ -101,40 +85,7 @@ class EASE(GeneralRecommender):
         nnz = int(row_ptr[-1])
         return sp.csr_matrix((val[:nnz], col[:nnz], row_ptr), shape=(self.user_num, self.item_num), dtype=np.float32)
 
-    # -- scores --------------------------------------------------------------------------------------------------------
-    def _check(self, ids, hi, what):
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= hi):
-            raise IndexError(f"index out of range: {what} ids must lie in [0, {hi})")
-
-    def _rank(self, users, items=None, topk=0):
-        self._fitted()
-        users = torch.as_tensor(users).reshape(-1).to(self.device, torch.int64)
-        self._check(users, self.user_num, "user")
-        if items is not None:
-            items = torch.as_tensor(items).to(self.device, torch.int64)
-            self._check(items, self.item_num, "item")
-        return ops.ease_rank(self._csr, self._B, users, items, topk)
-
-    def predict(self, u, i):
-        """EASERecommender.py:49-50 -> one float."""
-        return float(self._rank([int(u)], torch.tensor([[int(i)]], dtype=torch.int64))[0].cpu().item())
-
-    def rank(self, test_loader):
-        """EASERecommender.py:52-67 -> the candidates' ids int64 [n_users, topk], best first by predict's scores (the
-        reference's line 60 gathers B's rows where predict reads its columns: DESIGN.md §17)."""
-        self._fitted()
-        out = self._rank_loader(test_loader, lambda us, cands_ids: self._rank(us, cands_ids, self.topk)[1])
-        return out.astype(np.int64)                                  # (the reference returns the int64 ids)
-
-    def full_rank(self, u):
-        """EASERecommender.py:69-71 -> int64 [topk] over all items."""
-        return self._rank([int(u)], None, self.topk)[1].view(-1).cpu().numpy()
-
-    def full_rank_users(self, users, exclude=None, return_scores=False):
-        """Full ranking of many users in one launch (no counterpart in the reference): device int64
-        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
-        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
-        return_scores: (ids, float64 scores)."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        return ops.ease_full_rank_users(self._csr, self._B, users, self.topk, exclude=exclude, return_scores=return_scores)
+    # -- scores: FrameRecommender's, on X[u, :] B (EASERecommender.py:49-71; rank orders the candidates by predict's scores,
+    # where the reference's line 60 gathers B's rows: DESIGN.md §17) -------------------------------------------------------
+    def _operands(self):
+        return self._csr, self._B

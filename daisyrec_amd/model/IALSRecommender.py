@@ -16,13 +16,13 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .. import _native as N
 from .AbstractRecommender import GeneralRecommender
+from ._frame import frame_columns
 
 
 class IALS(GeneralRecommender):
@@ -67,24 +67,12 @@ class IALS(GeneralRecommender):
     # -- fit -----------------------------------------------------------------------------------------------------------
     def _frame_columns(self, df):
         """the configured columns: ids range-checked, ratings finite and >= 0"""
-        cols = []
-        for name, hi, what in ((self.uid_name, self.user_num, "user"), (self.iid_name, self.item_num, "item")):
-            ids = np.asarray(df[name])
-            if ids.size and not np.issubdtype(ids.dtype, np.integer):
-                if not np.all(ids == np.floor(ids)):
-                    raise ValueError(f"IALS.fit: column '{name}' holds non-integer ids")
-            ids = ids.astype(np.int64)
-            if ids.size and (ids.min() < 0 or ids.max() >= hi):
-                bad = ids.max() if ids.max() >= hi else ids.min()
-                raise ValueError(f"IALS.fit: {what} id {int(bad)} outside [0, {hi})")
-            cols.append(ids)
-        ratings = np.asarray(df[self.inter_name], dtype=np.float64)
-        if not np.all(np.isfinite(ratings)):
-            raise ValueError(f"IALS.fit: column '{self.inter_name}' holds a value that is not finite")
+        users, items, ratings = frame_columns(df, (self.uid_name, self.iid_name, self.inter_name), self.user_num,
+                                              self.item_num, "IALS")
         if ratings.size and ratings.min() < 0:
             raise ValueError(f"IALS.fit: column '{self.inter_name}' holds a negative value ({ratings.min()}): a confidence "
                              "1 + alpha r below 1 is outside the model")
-        return cols[0], cols[1], ratings
+        return users, items, ratings
 
     def _tables(self):
         """(P, Q): the weights on the device, contiguous"""

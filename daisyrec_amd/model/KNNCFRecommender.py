@@ -19,14 +19,16 @@ candidates.
 from __future__ import annotations
 
 import numpy as np
-import torch
 
 from .. import ops
-from .AbstractRecommender import GeneralRecommender
+from ._frame import FrameRecommender
 
 
-class _KNNCF(GeneralRecommender):
+class _KNNCF(FrameRecommender):
     _name = "KNNCF"
+    _rank_op = staticmethod(ops.knn_rank)
+    _users_op = staticmethod(ops.knn_full_rank_users)
+    _positions_op = staticmethod(ops.knn_full_rank_positions)
 
     def __init__(self, config):
         """Config keys as in KNNCFRecommender.py:402-413 / :481-491 (itemknn.yaml + basic.yaml)."""
@@ -54,34 +56,12 @@ class _KNNCF(GeneralRecommender):
         self.fit_info = None
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _frame_columns(self, df):
-        """KNNCFRecommender.py:36-38: the literal columns 'rating', 'user', 'item', range-checked."""
-        cols = []
-        for name, hi in (("user", self.user_num), ("item", self.item_num)):
-            ids = np.asarray(df[name])
-            if ids.size and not np.issubdtype(ids.dtype, np.integer):
-                if not np.all(ids == np.floor(ids)):
-                    raise ValueError(f"{self._name}.fit: column '{name}' holds non-integer ids")
-            ids = ids.astype(np.int64)
-            if ids.size and (ids.min() < 0 or ids.max() >= hi):
-                bad = ids.max() if ids.max() >= hi else ids.min()
-                raise ValueError(f"{self._name}.fit: {name} id {int(bad)} outside [0, {hi})")
-            cols.append(ids)
-        ratings = np.asarray(df["rating"], dtype=np.float64)
-        if not np.all(np.isfinite(ratings)):
-            raise ValueError(f"{self._name}.fit: column 'rating' holds a value that is not finite")
-        return cols[0], cols[1], ratings
-
     def _similarity_of(self, csr, csr_t):
         raise NotImplementedError
 
     def fit(self, train_set):
-        users, items, ratings = self._frame_columns(train_set)
-        self._require_device()
-        dev = torch.device(self.device)
-        u, i, r = (torch.from_numpy(a).to(dev) for a in (users, items, ratings))
-        csr = ops.slim_csr(u, i, r, self.user_num, self.item_num)
-        csr_t = ops.slim_csr(i, u, r, self.item_num, self.user_num)
+        """The frame's columns are 'user', 'item', 'rating' (KNNCFRecommender.py:36-38 names them literally)."""
+        csr, csr_t = self._frame_csr(train_set, transposed=True)
         self._W = None
         W, n, rows_d = self._similarity_of(csr, csr_t)
         self._csr, self._csr_t, self._W = csr, csr_t, W
@@ -97,10 +77,8 @@ class _KNNCF(GeneralRecommender):
             raise ValueError(f"{self._name}: min(maxk, n)={k} above {ops.N.KNN_MAX_K}")
         return ops.knn_fit(csr_D, n, self.similarity, self.shrink, k, normalize=self.normalize, csr_Dt=csr_Dt)
 
-    def _fitted(self):
-        self._require_device()
-        if self._W is None:
-            raise RuntimeError(f"{self._name}: fit(train_set) has not been called")
+    def _has_fit(self):
+        return self._W is not None
 
     # -- the reference's attributes, built on demand -------------------------------------------------------------------
     @property
@@ -122,53 +100,9 @@ class _KNNCF(GeneralRecommender):
         full = self._rank(np.arange(self.user_num), None, 0)[0].cpu().numpy()
         return sp.csr_matrix(full).tolil()
 
-    # -- scores --------------------------------------------------------------------------------------------------------
-    def _check(self, ids, hi, what):
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= hi):
-            raise IndexError(f"index out of range: {what} ids must lie in [0, {hi})")
-
-    def _rank(self, users, items=None, topk=0):
-        self._fitted()
-        users = torch.as_tensor(users).reshape(-1).to(self.device, torch.int64)
-        self._check(users, self.user_num, "user")
-        if items is not None:
-            items = torch.as_tensor(items).to(self.device, torch.int64)
-            self._check(items, self.item_num, "item")
-        return ops.knn_rank(self._L, self._R, self._inner, self.item_num, users, items, topk)
-
-    def predict(self, u, i):
-        """KNNCFRecommender.py:434-438 -> one float."""
-        return float(self._rank([int(u)], torch.tensor([[int(i)]], dtype=torch.int64))[0].cpu().item())
-
-    def rank(self, test_loader):
-        """KNNCFRecommender.py:440-452 -> the candidates' ids int64 [n_users, topk], best first."""
-        self._fitted()
-        out = self._rank_loader(test_loader, lambda us, cands_ids: self._rank(us, cands_ids, self.topk)[1])
-        return out.astype(np.int64)
-
-    def full_rank(self, u):
-        """KNNCFRecommender.py:454-457 -> int64 [topk] over all items."""
-        return self._rank([int(u)], None, self.topk)[1].view(-1).cpu().numpy()
-
-    def full_rank_users(self, users, exclude=None, return_scores=False):
-        """Full ranking of many users in one launch (no counterpart in the reference): device int64
-        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
-        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
-        return_scores: (ids, float64 scores)."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        return ops.knn_full_rank_users(self._L, self._R, self._inner, self.item_num, users, self.topk, exclude=exclude,
-                                       return_scores=return_scores)
-
-    def full_rank_positions(self, users, targets, exclude=None, **kw):
-        """The exact rank of every held-out item among all eligible items, in one launch (no counterpart in the
-        reference): `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets (test_ur /
-        train_ur); -> ops.full_rank_positions' tuple, consistent with full_rank_users - its ids[b, pos] is the target
-        wherever pos < topk - without the cap on topk.  kw: return_scores, return_eligible, validate, path."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        _, targets = self._users_and_exclusion(users, targets, self.user_num, self.device)
-        return ops.knn_full_rank_positions(self._L, self._R, self._inner, self.item_num, users, targets, exclude=exclude, **kw)
+    # -- scores: FrameRecommender's, on L[u, :] R (KNNCFRecommender.py:434-457) -----------------------------------------
+    def _operands(self):
+        return self._L, self._R, self._inner, self.item_num
 
 
 class ItemKNNCF(_KNNCF):

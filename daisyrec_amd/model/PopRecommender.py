@@ -19,6 +19,7 @@ import torch
 
 from .. import ops
 from .AbstractRecommender import GeneralRecommender
+from ._frame import id_column
 
 
 class MostPop(GeneralRecommender):
@@ -35,20 +36,9 @@ class MostPop(GeneralRecommender):
         self._cnt = self._score = None
         self._full = None           # full_rank's list: the same for every user
 
-    def _item_column(self, df):
-        """PopRecommender.py:30: the column config['IID_NAME'], range-checked."""
-        ids = np.asarray(df[self.cnt_col])
-        if ids.size and not np.issubdtype(ids.dtype, np.integer):
-            if not np.all(ids == np.floor(ids)):
-                raise ValueError(f"MostPop.fit: column '{self.cnt_col}' holds non-integer ids")
-        ids = ids.astype(np.int64)
-        if ids.size and (ids.min() < 0 or ids.max() >= self.item_num):
-            bad = ids.max() if ids.max() >= self.item_num else ids.min()
-            raise ValueError(f"MostPop.fit: {self.cnt_col} id {int(bad)} outside [0, {self.item_num})")
-        return ids
-
     def fit(self, train_set):
-        ids = self._item_column(train_set)
+        """PopRecommender.py:30-33: the counts of the column config['IID_NAME'], range-checked."""
+        ids = id_column(train_set, self.cnt_col, self.item_num, "MostPop", self.cnt_col)
         self._require_device()
         self._cnt, self._score = ops.pop_fit(torch.from_numpy(ids).to(self.device), self.item_num)
         self._full = None

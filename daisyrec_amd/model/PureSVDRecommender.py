@@ -19,13 +19,18 @@ import torch
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender
+from ._frame import FrameRecommender
 
 _OVERSAMPLES = 10          # randomized_svd's n_oversamples
 _SEED = 2019               # PureSVDRecommender.py:44
 
 
-class PureSVD(GeneralRecommender):
+class PureSVD(FrameRecommender):
+    _name = "PureSVD"
+    _rank_op = staticmethod(ops.psvd_rank)
+    _users_op = staticmethod(ops.psvd_full_rank_users)
+    _positions_op = staticmethod(ops.psvd_full_rank_positions)
+
     def __init__(self, config):
         """Config keys as in PureSVDRecommender.py:28-36 (puresvd.yaml + basic.yaml); ``puresvd_max_sweeps`` (60) bounds
         the Jacobi sweeps of the small SVD."""
@@ -50,34 +55,14 @@ class PureSVD(GeneralRecommender):
         self.logger.info(f"user num: {self.user_num}, item num: {self.item_num}")
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _frame_columns(self, df):
-        """PureSVDRecommender.py:51-58: the columns 'user', 'item', 'rating' (hard-coded there), range-checked."""
-        cols = []
-        for name, hi in (("user", self.user_num), ("item", self.item_num)):
-            ids = np.asarray(df[name])
-            if ids.size and not np.issubdtype(ids.dtype, np.integer):
-                if not np.all(ids == np.floor(ids)):
-                    raise ValueError(f"PureSVD.fit: column '{name}' holds non-integer ids")
-            ids = ids.astype(np.int64)
-            if ids.size and (ids.min() < 0 or ids.max() >= hi):
-                bad = ids.max() if ids.max() >= hi else ids.min()
-                raise ValueError(f"PureSVD.fit: {name} id {int(bad)} outside [0, {hi})")
-            cols.append(ids)
-        ratings = np.asarray(df["rating"], dtype=np.float64)
-        if not np.all(np.isfinite(ratings)):
-            raise ValueError("PureSVD.fit: column 'rating' holds a value that is not finite")
-        return cols[0], cols[1], ratings
-
     def fit(self, train_set):
-        """PureSVDRecommender.py:38-49: randomized_svd of the rating matrix; user_vec = U, item_vec = V diag(sigma)."""
-        users, items, ratings = self._frame_columns(train_set)
-        self._require_device()
+        """PureSVDRecommender.py:38-49: randomized_svd of the rating matrix; user_vec = U, item_vec = V diag(sigma).
+        The frame's columns are 'user', 'item', 'rating' (PureSVDRecommender.py:51-58 hard-codes them)."""
+        x, xt = self._frame_csr(train_set, transposed=True)
         self.logger.info("Computing SVD decomposition...")
+        self.logger.info('Finish build train matrix for decomposition')
         dev = torch.device(self.device)
         U, I, k = self.user_num, self.item_num, self.factors
-        u, i, r = (torch.from_numpy(a).to(dev) for a in (users, items, ratings))
-        x, xt = ops.slim_csr(u, i, r, U, I), ops.slim_csr(i, u, r, I, U)
-        self.logger.info('Finish build train matrix for decomposition')
         transposed = U < I                                            # randomized_svd: transpose='auto'
         n_iter = 7 if k < 0.1 * min(U, I) else 4                      # randomized_svd: n_iter='auto'
         m_csr, mt_csr, m = (xt, x, U) if transposed else (x, xt, I)   # M [n, m], n >= m
@@ -97,10 +82,8 @@ class PureSVD(GeneralRecommender):
                                "(config['puresvd_max_sweeps'])")
         self.logger.info('Done!')
 
-    def _fitted(self):
-        self._require_device()
-        if self._user_vec is None:
-            raise RuntimeError("PureSVD: fit(train_set) has not been called")
+    def _has_fit(self):
+        return self._user_vec is not None
 
     # -- the reference's attributes, fetched on access -----------------------------------------------------------------
     @property
@@ -113,26 +96,13 @@ class PureSVD(GeneralRecommender):
         """PureSVDRecommender.py:48: float64 [item_num, factors] (V diag(sigma)); None before fit."""
         return None if self._item_vec is None else self._item_vec.cpu().numpy()
 
-    # -- scores --------------------------------------------------------------------------------------------------------
-    def _check(self, ids, hi, what):
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= hi):
-            raise IndexError(f"index out of range: {what} ids must lie in [0, {hi})")
-
-    def _rank(self, users, items=None, topk=0):
-        self._fitted()
-        users = torch.as_tensor(users).reshape(-1).to(self.device, torch.int64)
-        self._check(users, self.user_num, "user")
-        if items is not None:
-            items = torch.as_tensor(items).to(self.device, torch.int64)
-            self._check(items, self.item_num, "item")
-        return ops.psvd_rank(self._user_vec, self._item_vec, users, items, topk)
-
-    def predict(self, u, i):
-        """PureSVDRecommender.py:60-61 -> one float."""
-        return float(self._rank([int(u)], torch.tensor([[int(i)]], dtype=torch.int64))[0].cpu().item())
+    # -- scores: FrameRecommender's, on <user_vec[u], item_vec[i]> (PureSVDRecommender.py:60-83) ------------------------
+    def _operands(self):
+        return self._user_vec, self._item_vec
 
     def rank(self, test_loader):
-        """PureSVDRecommender.py:63-78 -> the candidates' ids int64 [n_users, topk], best first."""
+        """PureSVDRecommender.py:63-78 -> the candidates' ids int64 [n_users, topk], best first ((0, topk) for an empty
+        loader)."""
         self._fitted()
         out = []
         for us, cands_ids in test_loader:                 # (not _rank_loader: it returns float32, the reference int64)
@@ -143,27 +113,3 @@ class PureSVD(GeneralRecommender):
         if not out:
             return np.zeros((0, self.topk), dtype=np.int64)
         return torch.cat(out, 0).cpu().numpy()
-
-    def full_rank(self, u):
-        """PureSVDRecommender.py:80-83 -> int64 [topk] over all items."""
-        return self._rank([int(u)], None, self.topk)[1].view(-1).cpu().numpy()
-
-    def full_rank_users(self, users, exclude=None, return_scores=False):
-        """Full ranking of many users in one launch (no counterpart in the reference): device int64
-        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
-        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
-        return_scores: (ids, float64 scores)."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        return ops.psvd_full_rank_users(self._user_vec, self._item_vec, users, self.topk, exclude=exclude,
-                                        return_scores=return_scores)
-
-    def full_rank_positions(self, users, targets, exclude=None, **kw):
-        """The exact rank of every held-out item among all eligible items, in one launch (no counterpart in the
-        reference): `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets (test_ur /
-        train_ur); -> ops.full_rank_positions' tuple, consistent with full_rank_users - its ids[b, pos] is the target
-        wherever pos < topk - without the cap on topk.  kw: return_scores, return_eligible, validate."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        _, targets = self._users_and_exclusion(users, targets, self.user_num, self.device)
-        return ops.psvd_full_rank_positions(self._user_vec, self._item_vec, users, targets, exclude=exclude, **kw)

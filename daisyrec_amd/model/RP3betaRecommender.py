@@ -76,16 +76,15 @@ class RP3beta(_KNNCF):
         p = x.pow(alpha) * scale[rowid]
         return (row_ptr, col, p.to(torch.float32).contiguous()), scale.to(torch.float32)
 
-    def fit(self, train_set):
-        users, items, ratings = self._frame_columns(train_set)
+    def _frame_columns(self, df):
+        users, items, ratings = super()._frame_columns(df)
         if not self.implicit and ratings.size and ratings.min() <= 0:
             raise ValueError(f"{self._name}.fit: column 'rating' holds {ratings.min()}: a transition probability needs "
                              "ratings > 0 (implicit=True takes every stored pair as 1)")
-        self._require_device()
-        dev = torch.device(self.device)
-        u, i, r = (torch.from_numpy(a).to(dev) for a in (users, items, ratings))
-        csr = ops.slim_csr(u, i, r, self.user_num, self.item_num)
-        csr_t = ops.slim_csr(i, u, r, self.item_num, self.user_num)
+        return users, items, ratings
+
+    def fit(self, train_set):
+        csr, csr_t = self._frame_csr(train_set, transposed=True)
         if self.implicit:
             csr, csr_t = ((c[0], c[1], torch.ones_like(c[2])) for c in (csr, csr_t))
         n = self.item_num

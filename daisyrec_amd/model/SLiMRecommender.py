@@ -19,12 +19,16 @@ import torch
 
 from .. import ops
 from .. import _native as N
-from .AbstractRecommender import GeneralRecommender
+from ._frame import FrameRecommender
 
 _SLAB_BYTES = 256 << 20        # default config['slim_slab_bytes']
 
 
-class SLiM(GeneralRecommender):
+class SLiM(FrameRecommender):
+    _name = "SLiM"
+    _users_op = staticmethod(ops.slim_full_rank_users)
+    _positions_op = staticmethod(ops.slim_full_rank_positions)
+
     def __init__(self, config):
         """Config keys as in SLiMRecommender.py:28-57 (slim.yaml + basic.yaml); ``slim_tol`` (1e-4) and
         ``slim_max_iter`` (100) are the two values the reference hard-codes in its ElasticNet; ``slim_slab_bytes`` (256 MB)
@@ -55,32 +59,11 @@ class SLiM(GeneralRecommender):
         self.logger.info(f"user num: {self.user_num}, item num: {self.item_num}")
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _frame_columns(self, df):
-        """SLiMRecommender.py:148-157: the columns 'user', 'item', 'rating' (hard-coded there), range-checked."""
-        cols = []
-        for name, hi in (("user", self.user_num), ("item", self.item_num)):
-            ids = np.asarray(df[name])
-            if ids.size and not np.issubdtype(ids.dtype, np.integer):
-                if not np.all(ids == np.floor(ids)):
-                    raise ValueError(f"SLiM.fit: column '{name}' holds non-integer ids")
-            ids = ids.astype(np.int64)
-            if ids.size and (ids.min() < 0 or ids.max() >= hi):
-                bad = ids.max() if ids.max() >= hi else ids.min()
-                raise ValueError(f"SLiM.fit: {name} id {int(bad)} outside [0, {hi})")
-            cols.append(ids)
-        ratings = np.asarray(df["rating"], dtype=np.float64)
-        if not np.all(np.isfinite(ratings)):
-            raise ValueError("SLiM.fit: column 'rating' holds a value that is not finite")
-        return cols[0], cols[1], ratings
-
     def fit(self, train_set, verbose=True):
-        """SLiMRecommender.py:59-124: Gram matrix, the columns' elastic nets, truncation; W and X stay on the device."""
-        users, items, ratings = self._frame_columns(train_set)
-        self._require_device()
-        dev = torch.device(self.device)
+        """SLiMRecommender.py:59-124: Gram matrix, the columns' elastic nets, truncation; W and X stay on the device.
+        The frame's columns are 'user', 'item', 'rating' (SLiMRecommender.py:148-157 hard-codes them)."""
+        csr, _ = self._frame_csr(train_set)
         I, k = self.item_num, self.topk
-        csr = ops.slim_csr(torch.from_numpy(users).to(dev), torch.from_numpy(items).to(dev),
-                           torch.from_numpy(ratings).to(dev), self.user_num, I)
         G = ops.slim_gram(csr, I)
         chunk = max(1, min(I, self.slab_bytes // (8 * k)))
         parts = []
@@ -96,27 +79,21 @@ class SLiM(GeneralRecommender):
         self.fit_info = {"sweeps": sweeps.cpu().numpy(), "gap": gap.cpu().numpy()}
         del G
 
-    def _fitted(self):
-        self._require_device()
-        if self._W is None:
-            raise RuntimeError("SLiM: fit(train_set) has not been called")
+    def _has_fit(self):
+        return self._W is not None
 
-    # -- scores --------------------------------------------------------------------------------------------------------
+    # -- scores: float32, ranked through ops.topk_from_scores; full_rank_users and full_rank_positions are the base's ------
+    def _operands(self):
+        return self._csr, self._W, self.item_num
+
     def _check_users(self, users):
-        if users.numel() and (int(users.min()) < 0 or int(users.max()) >= self.user_num):
-            raise IndexError(f"index out of range: user ids must lie in [0, {self.user_num})")
+        self._check(users, self.user_num, "user")
 
     def _check_items(self, items):
-        if items.numel() and (int(items.min()) < 0 or int(items.max()) >= self.item_num):
-            raise IndexError(f"index out of range: item ids must lie in [0, {self.item_num})")
+        self._check(items, self.item_num, "item")
 
     def _scores(self, users, items=None):
-        self._fitted()
-        users = torch.as_tensor(users).reshape(-1).to(self.device, torch.int64)
-        self._check_users(users)
-        if items is not None:
-            items = torch.as_tensor(items).to(self.device, torch.int64)
-            self._check_items(items)
+        users, items = self._request(users, items)
         return ops.slim_scores(self._csr, self._W, self.item_num, users, items)
 
     def predict(self, u, i):
@@ -137,26 +114,6 @@ class SLiM(GeneralRecommender):
         """SLiMRecommender.py:143-146 -> int64 [topk] over all items."""
         scores = self._scores([int(u)])
         return ops.full_topk_from_scores(scores.view(-1), min(self.topk, self.item_num)).cpu().numpy()
-
-    def full_rank_users(self, users, exclude=None, return_scores=False):
-        """Full ranking of many users in one launch (no counterpart in the reference): device int64
-        [len(users), topk], row b = full_rank(users[b]) without the items of the user's row of `exclude` (None, an
-        (indptr, items) device CSR or a train_ur dict of sets); -1 where a user has fewer eligible items than topk.
-        return_scores: (ids, float32 scores)."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        return ops.slim_full_rank_users(self._csr, self._W, self.item_num, users, self.topk, exclude=exclude,
-                                        return_scores=return_scores)
-
-    def full_rank_positions(self, users, targets, exclude=None, **kw):
-        """The exact rank of every held-out item among all eligible items, in one launch (no counterpart in the
-        reference): `targets` and `exclude` are an (indptr, items) device CSR or a dict of sets (test_ur /
-        train_ur); -> ops.full_rank_positions' tuple, consistent with full_rank_users - its ids[b, pos] is the target
-        wherever pos < topk - without the cap on topk.  kw: return_scores, return_eligible, validate, path."""
-        self._fitted()
-        users, exclude = self._users_and_exclusion(users, exclude, self.user_num, self.device)
-        _, targets = self._users_and_exclusion(users, targets, self.user_num, self.device)
-        return ops.slim_full_rank_positions(self._csr, self._W, self.item_num, users, targets, exclude=exclude, **kw)
 
     # -- the reference's attributes, built on demand -------------------------------------------------------------------
     @property

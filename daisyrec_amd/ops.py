@@ -1636,28 +1636,54 @@ def slim_columns(count, rows, vals, item_num):
     return w_ptr, w_row, w_val
 
 
-def slim_scores(csr, W, item_num, users, items=None, path="auto"):
-    """Rows of A_tilde = X W for users [B] (daisy_slim_scores): float32 [B, C] at the candidates items [B, C] (int64), or
-    [B, item_num].  W: slim_columns' triple."""
+# _slim_operands, _psvd_operands, _ease_operands, _knn_operands: a family's shape checks, once -> (the
+# leading arguments of its C entries in their order, the user count, the item count, the device, the score dtype of its
+# full-rank entries, whether its entries end in a `path`); _f64_rank, _f64_full_rank_users and _f64_full_rank_positions
+# make the request of each kind and call the entry on them.
+def _slim_operands(csr, W, item_num):
     rp, cp, vp, U = _slim_csr_ptrs(csr)
     w_ptr, w_row, w_val = W
     I = int(item_num)
+    lead = (rp, cp, vp, U, I, _ptr(w_ptr, torch.int64, "w_ptr"), _ptr(w_row, torch.int32, "w_row"),
+            _ptr(w_val, torch.float32, "w_val"))
+    return lead, U, I, w_ptr.device, torch.float32, True
+
+
+def _candidates(users, items, n_items):
+    """The request of a *_rank / slim_scores call: (users int64 [B], B, items int64 [B, C] or None, C - n_items for None)."""
     users = users.to(torch.int64).contiguous()
     B = users.numel()
-    if items is not None:
-        items = items.to(torch.int64).contiguous()
-        if items.dim() != 2 or items.shape[0] != B:
-            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
-        Cn = int(items.shape[1])
-        out = torch.empty(B, Cn, dtype=torch.float32, device=users.device)
-    else:
-        Cn = 0
-        out = torch.empty(B, I, dtype=torch.float32, device=users.device)
-    check(lib.daisy_slim_scores(rp, cp, vp, U, I, _ptr(w_ptr, torch.int64, "w_ptr"), _ptr(w_row, torch.int32, "w_row"),
-                                _ptr(w_val, torch.float32, "w_val"), _ptr(users, torch.int64, "users"), B,
-                                _ptr(items, torch.int64, "items"), Cn, _ptr(out, torch.float32, "out"), N.SLIM_PATHS[path],
-                                _stream()))
+    if items is None:
+        return users, B, None, n_items
+    items = items.to(torch.int64).contiguous()
+    if items.dim() != 2 or items.shape[0] != B:
+        raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
+    return users, B, items, int(items.shape[1])
+
+
+def slim_scores(csr, W, item_num, users, items=None, path="auto"):
+    """Rows of A_tilde = X W for users [B] (daisy_slim_scores): float32 [B, C] at the candidates items [B, C] (int64), or
+    [B, item_num].  W: slim_columns' triple."""
+    lead, _, I, _, _, _ = _slim_operands(csr, W, item_num)
+    users, B, items, Cn = _candidates(users, items, I)
+    out = torch.empty(B, Cn, dtype=torch.float32, device=users.device)
+    check(lib.daisy_slim_scores(*lead, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"),
+                                0 if items is None else Cn, _ptr(out, torch.float32, "out"), N.SLIM_PATHS[path], _stream()))
     return out
+
+
+def _f64_rank(fn, operands, users, items, topk, path=None):
+    """What ease_rank, knn_rank and psvd_rank share: the request, the outputs and the call of `fn`, the family's
+    daisy_*_rank.  -> (scores float64 [B, C], ids int64 [B, min(topk, C)] or None)"""
+    lead, _, I, dev, _, has_path = operands
+    users, B, items, Cn = _candidates(users, items, I)
+    scores = torch.empty(B, Cn, dtype=torch.float64, device=dev)
+    kk = min(int(topk), Cn)
+    ids = torch.empty(B, kk, dtype=torch.int64, device=dev) if kk > 0 else None
+    check(fn(*lead, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"), Cn, kk,
+             _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"),
+             *((N.SLIM_PATHS[path],) if has_path else ()), _stream()))
+    return scores, ids
 
 
 # ---- PureSVD (csrc/puresvd.hip; PureSVDRecommender.py; DESIGN.md §16) --------------------------------------------------------
@@ -1766,30 +1792,19 @@ def psvd_fit(csr, csr_t, omega, n_iter, max_sweeps=60):
     return psvd_gemm(Q, Uh), s, psvd_gemm(Q2, Vh), torch.cat(dropped), info
 
 
-def psvd_rank(user_vec, item_vec, users, items=None, topk=0):
-    """float64 scores [B, C] of users [B] at the candidates items [B, C] (None: every item) and, for topk > 0, the ids
-    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_psvd_rank).
-    -> (scores, ids or None)"""
+def _psvd_operands(user_vec, item_vec):
     up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
     U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
     if item_vec.shape[1] != k:
         raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
-    users = users.to(torch.int64).contiguous()
-    B = users.numel()
-    if items is not None:
-        items = items.to(torch.int64).contiguous()
-        if items.dim() != 2 or items.shape[0] != B:
-            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
-        Cn = int(items.shape[1])
-    else:
-        Cn = I
-    dev = user_vec.device
-    scores = torch.empty(B, Cn, dtype=torch.float64, device=dev)
-    kk = min(int(topk), Cn)
-    ids = torch.empty(B, kk, dtype=torch.int64, device=dev) if kk > 0 else None
-    check(lib.daisy_psvd_rank(up, ip, U, I, k, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"), Cn, kk,
-                              _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
-    return scores, ids
+    return (up, ip, U, I, k), U, I, user_vec.device, torch.float64, False
+
+
+def psvd_rank(user_vec, item_vec, users, items=None, topk=0):
+    """float64 scores [B, C] of users [B] at the candidates items [B, C] (None: every item) and, for topk > 0, the ids
+    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_psvd_rank).
+    -> (scores, ids or None)"""
+    return _f64_rank(lib.daisy_psvd_rank, _psvd_operands(user_vec, item_vec), users, items, topk)
 
 
 # ---- EASE (csrc/ease.hip; EASERecommender.py; DESIGN.md §17) ------------------------------------------------------------------
@@ -1867,27 +1882,17 @@ def ease_fit(csr, item_num, reg, offered_bytes=None):
     return ease_weights(P, ws, inplace=True), info
 
 
+def _ease_operands(csr, W):
+    rp, cp, vp, U = _slim_csr_ptrs(csr)
+    wp, I = _ease_square(W, "W")
+    return (rp, cp, vp, wp, U, I), U, I, W.device, torch.float64, False
+
+
 def ease_rank(csr, W, users, items=None, topk=0):
     """float64 scores [B, C] = X[users] W at the candidates items [B, C] (None: every item) and, for topk > 0, the ids
     int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_ease_rank).
     csr: slim_csr's triple of X; W float64 [I, I].  -> (scores, ids or None)"""
-    rp, cp, vp, U = _slim_csr_ptrs(csr)
-    wp, I = _ease_square(W, "W")
-    users = users.to(torch.int64).contiguous()
-    B = users.numel()
-    if items is not None:
-        items = items.to(torch.int64).contiguous()
-        if items.dim() != 2 or items.shape[0] != B:
-            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
-        Cn = int(items.shape[1])
-    else:
-        Cn = I
-    scores = torch.empty(B, Cn, dtype=torch.float64, device=W.device)
-    kk = min(int(topk), Cn)
-    ids = torch.empty(B, kk, dtype=torch.int64, device=W.device) if kk > 0 else None
-    check(lib.daisy_ease_rank(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), B, _ptr(items, torch.int64, "items"),
-                              Cn, kk, _ptr(scores, torch.float64, "scores"), _ptr(ids, torch.int64, "ids"), _stream()))
-    return scores, ids
+    return _f64_rank(lib.daisy_ease_rank, _ease_operands(csr, W), users, items, topk)
 
 
 # ---- iALS (csrc/ials.hip; IALSRecommender.py; DESIGN.md §29) -------------------------------------------------------------------
@@ -2097,31 +2102,19 @@ def knn_rows_of_columns(W, n):
     return ptr, col, val
 
 
-def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
-    """float64 scores [B, C] = L[users] R at the candidates items [B, C] (None: every column) and, for topk > 0, the ids
-    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_knn_rank).  L: a
-    CSR triple [*, inner]; R: a by-column triple [inner, n_cols].  -> (scores, ids or None)"""
+def _knn_operands(L, R, inner, n_cols):
     lp, lc, lv, n_rows = _slim_csr_ptrs(L)
     rp, rc, rv, nc = _slim_csr_ptrs(R)
     if nc != int(n_cols):
         raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
-    users = users.to(torch.int64).contiguous()
-    B = users.numel()
-    if items is not None:
-        items = items.to(torch.int64).contiguous()
-        if items.dim() != 2 or items.shape[0] != B:
-            raise ValueError(f"items: expected [{B}, C], got {tuple(items.shape)}")
-        Cn = int(items.shape[1])
-    else:
-        Cn = int(n_cols)
-    dev = L[0].device
-    scores = torch.empty(B, Cn, dtype=torch.float64, device=dev)
-    kk = min(int(topk), Cn)
-    ids = torch.empty(B, kk, dtype=torch.int64, device=dev) if kk > 0 else None
-    check(lib.daisy_knn_rank(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols), _ptr(users, torch.int64, "users"), B,
-                             _ptr(items, torch.int64, "items"), Cn, kk, _ptr(scores, torch.float64, "scores"),
-                             _ptr(ids, torch.int64, "ids"), N.SLIM_PATHS[path], _stream()))
-    return scores, ids
+    return (lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols)), n_rows, int(n_cols), L[0].device, torch.float64, True
+
+
+def knn_rank(L, R, inner, n_cols, users, items=None, topk=0, path="auto"):
+    """float64 scores [B, C] = L[users] R at the candidates items [B, C] (None: every column) and, for topk > 0, the ids
+    int64 [B, min(topk, C)] of the largest ones compared as float64, ties to the lower position (daisy_knn_rank).  L: a
+    CSR triple [*, inner]; R: a by-column triple [inner, n_cols].  -> (scores, ids or None)"""
+    return _f64_rank(lib.daisy_knn_rank, _knn_operands(L, R, inner, n_cols), users, items, topk, path)
 
 
 # ---- two-hop walk with a per-row top-K (csrc/walk2.hip; RP3betaRecommender.py; DESIGN.md §30) ---------------------------
@@ -2212,6 +2205,16 @@ def _rank_f64_users_args(users, user_num, topk, exclude, return_scores, validate
     return users, n, topk, excl, ids, scores, (indptr, items)
 
 
+def _f64_full_rank_users(fn, operands, users, topk, exclude, return_scores, validate, path=None):
+    """What the four *_full_rank_users share: `fn`, the family's daisy_*_full_rank_users, on its operands and the request."""
+    lead, U, _, dev, score_dtype, has_path = operands
+    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate, dev,
+                                                                    score_dtype)
+    check(fn(*lead, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk, _ptr(ids, torch.int64, "ids"),
+             _ptr(scores, score_dtype, "scores"), *((N.SLIM_PATHS[path],) if has_path else ()), _stream()))
+    return (ids, scores) if return_scores else ids
+
+
 def ease_full_rank_users(csr, W, users, topk, exclude=None, return_scores=False, validate=True):
     """Full ranking of many users by EASE's scores X[users] W in one launch (daisy_ease_full_rank_users):
     int64 [n, topk] device ids of the best items of ALL I, best first by the float64 score of ease_rank (the same bits),
@@ -2219,58 +2222,29 @@ def ease_full_rank_users(csr, W, users, topk, exclude=None, return_scores=False,
     [U + 1], items int32 ascending per row).  Positions beyond a user's eligible items hold -1 (score -inf); topk above I
     is allowed, above RANK_F64_TOPK_CAP a ValueError.  return_scores: (ids, float64 scores).  validate: as
     ops.full_rank_users.  No [n, I] array is written."""
-    rp, cp, vp, U = _slim_csr_ptrs(csr)
-    wp, I = _ease_square(W, "W")
-    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate, W.device,
-                                                                    torch.float64)
-    check(lib.daisy_ease_full_rank_users(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
-                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"), _stream()))
-    return (ids, scores) if return_scores else ids
+    return _f64_full_rank_users(lib.daisy_ease_full_rank_users, _ease_operands(csr, W), users, topk, exclude, return_scores,
+                                validate)
 
 
 def slim_full_rank_users(csr, W, item_num, users, topk, exclude=None, return_scores=False, validate=True, path="auto"):
     """ease_full_rank_users for SLiM (daisy_slim_full_rank_users): the ranking is on slim_scores' float32 values (the
     float64 sum rounded once), returned as float32.  W: slim_columns' triple; path as slim_scores."""
-    rp, cp, vp, U = _slim_csr_ptrs(csr)
-    w_ptr, w_row, w_val = W
-    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate,
-                                                                    w_ptr.device, torch.float32)
-    check(lib.daisy_slim_full_rank_users(rp, cp, vp, U, int(item_num), _ptr(w_ptr, torch.int64, "w_ptr"),
-                                         _ptr(w_row, torch.int32, "w_row"), _ptr(w_val, torch.float32, "w_val"),
-                                         _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
-                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float32, "scores"),
-                                         N.SLIM_PATHS[path], _stream()))
-    return (ids, scores) if return_scores else ids
+    return _f64_full_rank_users(lib.daisy_slim_full_rank_users, _slim_operands(csr, W, item_num), users, topk, exclude,
+                                return_scores, validate, path)
 
 
 def knn_full_rank_users(L, R, inner, n_cols, users, topk, exclude=None, return_scores=False, validate=True, path="auto"):
     """ease_full_rank_users for ItemKNN / UserKNN (daisy_knn_full_rank_users): the float64 scores L[users] R of knn_rank.
     L: a CSR triple [U, inner]; R: a by-column triple [inner, n_cols]; path as knn_rank."""
-    lp, lc, lv, n_rows = _slim_csr_ptrs(L)
-    rp, rc, rv, nc = _slim_csr_ptrs(R)
-    if nc != int(n_cols):
-        raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
-    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, n_rows, topk, exclude, return_scores, validate,
-                                                                    L[0].device, torch.float64)
-    check(lib.daisy_knn_full_rank_users(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols),
-                                        _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
-                                        _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"),
-                                        N.SLIM_PATHS[path], _stream()))
-    return (ids, scores) if return_scores else ids
+    return _f64_full_rank_users(lib.daisy_knn_full_rank_users, _knn_operands(L, R, inner, n_cols), users, topk, exclude,
+                                return_scores, validate, path)
 
 
 def psvd_full_rank_users(user_vec, item_vec, users, topk, exclude=None, return_scores=False, validate=True):
     """ease_full_rank_users for PureSVD (daisy_psvd_full_rank_users): the float64 scores <user_vec[u], item_vec[i]> of
     psvd_rank."""
-    up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
-    U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
-    if item_vec.shape[1] != k:
-        raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
-    users, n, topk, excl, ids, scores, _keep = _rank_f64_users_args(users, U, topk, exclude, return_scores, validate,
-                                                                    user_vec.device, torch.float64)
-    check(lib.daisy_psvd_full_rank_users(up, ip, U, I, k, _ptr(users, torch.int64, "users"), n, excl[0], excl[1], topk,
-                                         _ptr(ids, torch.int64, "ids"), _ptr(scores, torch.float64, "scores"), _stream()))
-    return (ids, scores) if return_scores else ids
+    return _f64_full_rank_users(lib.daisy_psvd_full_rank_users, _psvd_operands(user_vec, item_vec), users, topk, exclude,
+                                return_scores, validate)
 
 
 # ---- exact ranks of held-out items on fp64 scores (csrc/rank_positions_f64.hip; DESIGN.md §28) ----------------------------
@@ -2329,6 +2303,18 @@ def _rank_positions_out(out_indptr, pos, scores, eligible):
     return out
 
 
+def _f64_full_rank_positions(fn, operands, users, targets, exclude, return_scores, return_eligible, validate, path=None):
+    """What the four *_full_rank_positions share: `fn`, the family's daisy_*_full_rank_positions, on its operands and the
+    request."""
+    lead, U, _, dev, score_dtype, has_path = operands
+    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
+        users, U, targets, exclude, return_scores, return_eligible, validate, dev, score_dtype)
+    check(fn(*lead, _ptr(users, torch.int64, "users"), n, *ptrs, _ptr(out_indptr, torch.int64, "out_indptr"), T,
+             _ptr(pos, torch.int32, "positions"), _ptr(scores, score_dtype, "scores"), _ptr(eligible, torch.int32, "eligible"),
+             *((N.SLIM_PATHS[path],) if has_path else ()), _stream()))
+    return _rank_positions_out(out_indptr, pos, scores, eligible)
+
+
 def ease_full_rank_positions(csr, W, users, targets, exclude=None, return_scores=False, return_eligible=False, validate=True):
     """The exact 0-based rank of every held-out item among ALL eligible items by EASE's scores X[users] W, in one launch
     (daisy_ease_full_rank_positions): for request b = users[b] and every item t of the user's row of
@@ -2340,67 +2326,32 @@ def ease_full_rank_positions(csr, W, users, targets, exclude=None, return_scores
     eligible = the items a user can be recommended.  validate: ops.full_rank_positions' checks on users, exclude and
     targets; False skips them - the kernel then trusts the user ids and the indptr arrays, only compares the exclusion's
     contents and range-checks every target id.  No [n, I] array is written."""
-    rp, cp, vp, U = _slim_csr_ptrs(csr)
-    wp, I = _ease_square(W, "W")
-    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
-        users, U, targets, exclude, return_scores, return_eligible, validate, W.device, torch.float64)
-    check(lib.daisy_ease_full_rank_positions(rp, cp, vp, wp, U, I, _ptr(users, torch.int64, "users"), n, *ptrs,
-                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
-                                             _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
-                                             _stream()))
-    return _rank_positions_out(out_indptr, pos, scores, eligible)
+    return _f64_full_rank_positions(lib.daisy_ease_full_rank_positions, _ease_operands(csr, W), users, targets, exclude,
+                                    return_scores, return_eligible, validate)
 
 
 def slim_full_rank_positions(csr, W, item_num, users, targets, exclude=None, return_scores=False, return_eligible=False,
                              validate=True, path="auto"):
     """ease_full_rank_positions for SLiM (daisy_slim_full_rank_positions): the ranks are on slim_scores' float32 values (the
     float64 sum rounded once), returned as float32.  W: slim_columns' triple; path as slim_scores."""
-    rp, cp, vp, U = _slim_csr_ptrs(csr)
-    w_ptr, w_row, w_val = W
-    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
-        users, U, targets, exclude, return_scores, return_eligible, validate, w_ptr.device, torch.float32)
-    check(lib.daisy_slim_full_rank_positions(rp, cp, vp, U, int(item_num), _ptr(w_ptr, torch.int64, "w_ptr"),
-                                             _ptr(w_row, torch.int32, "w_row"), _ptr(w_val, torch.float32, "w_val"),
-                                             _ptr(users, torch.int64, "users"), n, *ptrs,
-                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
-                                             _ptr(scores, torch.float32, "scores"), _ptr(eligible, torch.int32, "eligible"),
-                                             N.SLIM_PATHS[path], _stream()))
-    return _rank_positions_out(out_indptr, pos, scores, eligible)
+    return _f64_full_rank_positions(lib.daisy_slim_full_rank_positions, _slim_operands(csr, W, item_num), users, targets,
+                                    exclude, return_scores, return_eligible, validate, path)
 
 
 def knn_full_rank_positions(L, R, inner, n_cols, users, targets, exclude=None, return_scores=False, return_eligible=False,
                             validate=True, path="auto"):
     """ease_full_rank_positions for ItemKNN / UserKNN (daisy_knn_full_rank_positions): the float64 scores L[users] R of
     knn_rank.  L: a CSR triple [U, inner]; R: a by-column triple [inner, n_cols]; path as knn_rank."""
-    lp, lc, lv, n_rows = _slim_csr_ptrs(L)
-    rp, rc, rv, nc = _slim_csr_ptrs(R)
-    if nc != int(n_cols):
-        raise ValueError(f"R: {nc} columns given, n_cols={n_cols}")
-    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
-        users, n_rows, targets, exclude, return_scores, return_eligible, validate, L[0].device, torch.float64)
-    check(lib.daisy_knn_full_rank_positions(lp, lc, lv, n_rows, int(inner), rp, rc, rv, int(n_cols),
-                                            _ptr(users, torch.int64, "users"), n, *ptrs,
-                                            _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
-                                            _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
-                                            N.SLIM_PATHS[path], _stream()))
-    return _rank_positions_out(out_indptr, pos, scores, eligible)
+    return _f64_full_rank_positions(lib.daisy_knn_full_rank_positions, _knn_operands(L, R, inner, n_cols), users, targets,
+                                    exclude, return_scores, return_eligible, validate, path)
 
 
 def psvd_full_rank_positions(user_vec, item_vec, users, targets, exclude=None, return_scores=False, return_eligible=False,
                              validate=True):
     """ease_full_rank_positions for PureSVD (daisy_psvd_full_rank_positions): the float64 scores <user_vec[u], item_vec[i]>
     of psvd_rank."""
-    up, ip = _f64(user_vec, "user_vec"), _f64(item_vec, "item_vec")
-    U, k, I = int(user_vec.shape[0]), int(user_vec.shape[1]), int(item_vec.shape[0])
-    if item_vec.shape[1] != k:
-        raise ValueError(f"item_vec: expected [I, {k}], got {tuple(item_vec.shape)}")
-    users, n, T, ptrs, out_indptr, pos, scores, eligible, _keep = _rank_positions_args(
-        users, U, targets, exclude, return_scores, return_eligible, validate, user_vec.device, torch.float64)
-    check(lib.daisy_psvd_full_rank_positions(up, ip, U, I, k, _ptr(users, torch.int64, "users"), n, *ptrs,
-                                             _ptr(out_indptr, torch.int64, "out_indptr"), T, _ptr(pos, torch.int32, "positions"),
-                                             _ptr(scores, torch.float64, "scores"), _ptr(eligible, torch.int32, "eligible"),
-                                             _stream()))
-    return _rank_positions_out(out_indptr, pos, scores, eligible)
+    return _f64_full_rank_positions(lib.daisy_psvd_full_rank_positions, _psvd_operands(user_vec, item_vec), users, targets,
+                                    exclude, return_scores, return_eligible, validate)
 
 
 # ---- masked top-k over rows of fp32 scores (csrc/rank_rows.hip; DESIGN.md §26) --------------------------------------------
