@@ -12,14 +12,11 @@
 // not depend on append order, wave scheduling or the slice count.
 #include "common.h"
 #include "mfma.h"
-#include "rank_key_f32.h"                       // fr_key / fr_unkey: the score half of the sort word
+#include "rank_key_f32.h"                       // fr_word: the sort word and its halves
+#include "rank_tiles_f32.h"                     // the kRt* tile and the helpers shared with k_frp_count
 
 namespace daisy {
 
-constexpr int kFrBM = 128;                      // items per tile (MFMA M side)
-constexpr int kFrBN = 64;                       // users per tile (MFMA N side)
-constexpr int kFrBK = 16;                       // k depth of an LDS tile
-constexpr int kFrLA = kFrBM + 4, kFrLB = kFrBN + 4;
 constexpr int kFrTopkCap = 128;                 // the contract's cap: candidate buffers of 64 users live in LDS
 constexpr int kFrSort = 256;                    // words one wave sorts: 4 per lane
 constexpr int kFrBuf = 224;                     // candidate words per user
@@ -27,15 +24,12 @@ constexpr int kFrStep = 64;                     // most words ONE epilogue step 
 constexpr int kFrLimit = kFrBuf - kFrStep;      // a buffer holding more than this is compacted before the next step
 static_assert(kFrLimit >= kFrTopkCap && kFrBuf <= kFrSort, "a compacted buffer must leave room for one step");
 
-constexpr int kFrLdsBytes = kFrBN * kFrBuf * 8 + 2 * kFrBK * (kFrLA + kFrLB) * 4 + kFrBN * (4 * 4 + 8 * 4 + 4);
-constexpr int kFrAhead = 4;                     // chunks in flight from memory ahead of the one in LDS
-constexpr int kFrTargetGroups = 512;            // item slices are added until the grid has about this many workgroups
-
-__device__ __forceinline__ uint64_t fr_shfl_xor(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, kWave);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, kWave);
-    return ((uint64_t)hi << 32) | lo;
-}
+// candidate buffers, the operand stages and ONE exclusion mask (the epilogue's barrier frees it for the next tile), and
+// per user the threshold, exclusion cursor, row end, user id and count
+constexpr int kFrLdsBytes = kRtBN * kFrBuf * 8 + kRtStageBytes + kRtMaskBytes + kRtBN * (8 * 4 + 4);
+// item slices are added until the grid has about this many workgroups (one workgroup per CU is resident: its candidate
+// buffers take most of the LDS)
+constexpr int kFrTargetGroups = 512;
 
 // 256 words of a wave, element e = lane * 4 + r in w[r], into descending order: a bitonic network whose strides below
 // 4 stay inside the lane and whose wider ones are one lane exchange per word.  No LDS, no barrier.
@@ -48,7 +42,7 @@ __device__ __forceinline__ void fr_sort_desc(uint64_t (&w)[4], int lane) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int e = lane * 4 + r;
-                    const uint64_t o = fr_shfl_xor(w[r], j >> 2);
+                    const uint64_t o = rt_shfl_xor(w[r], j >> 2);
                     const bool keep_max = ((e & j) == 0) == ((e & k) == 0);
                     const uint64_t hi = (w[r] > o) ? w[r] : o, lo = (w[r] > o) ? o : w[r];
                     w[r] = keep_max ? hi : lo;
@@ -100,23 +94,23 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
     int64_t n_tiles, int S, uint64_t *__restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fr_lds[];
     uint64_t *buf = reinterpret_cast<uint64_t *>(fr_lds);                       // [64][kFrBuf]
-    float *As = reinterpret_cast<float *>(buf + kFrBN * kFrBuf);                // [2][kFrBK * kFrLA]
-    float *Bs = As + 2 * kFrBK * kFrLA;                                         // [2][kFrBK * kFrLB]
-    uint32_t *mask = reinterpret_cast<uint32_t *>(Bs + 2 * kFrBK * kFrLB);      // [64][4]: bit = item of the tile
-    uint64_t *thr = reinterpret_cast<uint64_t *>(mask + kFrBN * 4);             // [64] k-th best word so far (0: none)
-    int64_t *cur = reinterpret_cast<int64_t *>(thr + kFrBN);                    // [64] the slice's first cursor into the exclusion
-    int64_t *end = cur + kFrBN;                                                 // [64] row and the row's end (read once, below)
-    int64_t *uid = end + kFrBN;                                                 // [64] user id of the slot, -1: past n
-    int *cnt = reinterpret_cast<int *>(uid + kFrBN);                            // [64] words in the buffer
+    float *As = reinterpret_cast<float *>(buf + kRtBN * kFrBuf);                // [2][kRtBK * kRtLA]
+    float *Bs = As + 2 * kRtBK * kRtLA;                                         // [2][kRtBK * kRtLB]
+    uint32_t *mask = reinterpret_cast<uint32_t *>(Bs + 2 * kRtBK * kRtLB);      // [64][4]: bit = item of the tile
+    uint64_t *thr = reinterpret_cast<uint64_t *>(mask + kRtBN * 4);             // [64] k-th best word so far (0: none)
+    int64_t *cur = reinterpret_cast<int64_t *>(thr + kRtBN);                    // [64] the slice's first cursor into the exclusion
+    int64_t *end = cur + kRtBN;                                                 // [64] row and the row's end (read once, below)
+    int64_t *uid = end + kRtBN;                                                 // [64] user id of the slot, -1: past n
+    int *cnt = reinterpret_cast<int *>(uid + kRtBN);                            // [64] words in the buffer
 
     const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
     const int wm = wave / 2, wn = wave % 2;
-    const int64_t u0 = (int64_t)blockIdx.x * kFrBN;
+    const int64_t u0 = (int64_t)blockIdx.x * kRtBN;
     const int s = blockIdx.y;
     const int64_t t_lo = (int64_t)s * tiles_per_slice;
     const int64_t t_hi = (t_lo + tiles_per_slice < n_tiles) ? (t_lo + tiles_per_slice) : n_tiles;
 
-    if (tid < kFrBN) {
+    if (tid < kRtBN) {
         const int64_t slot = u0 + tid;
         const int64_t u = (slot < n) ? users[slot] : -1;
         uid[tid] = u;
@@ -124,16 +118,8 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
         thr[tid] = 0ull;
         int64_t lo = 0, hi = 0;
         if (indptr && u >= 0) {
-            lo = indptr[u];
             hi = indptr[u + 1];
-            const int64_t first = t_lo * kFrBM;             // lower bound of the slice's first item: contents are
-            int64_t a = lo, b = hi;                         // only compared, so an unsorted row costs exclusions, no more
-            while (a < b) {
-                const int64_t m = a + (b - a) / 2;
-                if ((int64_t)eitems[m] < first) a = m + 1;
-                else b = m;
-            }
-            lo = a;
+            lo = rt_lower_bound(eitems, indptr[u], hi, t_lo * kRtBM);       // the slice's first item
         }
         cur[tid] = lo;
         end[tid] = hi;
@@ -149,14 +135,14 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
     float ep_bu = 0.f, ep_b0 = 0.f;
     if (bu && ep_uid >= 0) { ep_bu = bu[ep_uid]; ep_b0 = b0[0]; }
     const int kk = (tid % 4) * 4;
-    const int n_k = (d + kFrBK - 1) / kFrBK;
+    const int n_k = (d + kRtBK - 1) / kRtBK;
     // The workgroup's work is ONE stream of chunks, (item tile, k chunk) with the tile outermost.  Chunk g sits in LDS
-    // stage g & 1; chunks g + 1 .. g + kFrAhead are in flight from memory into a ring of registers (slot = chunk %
-    // kFrAhead), so a load has three chunks of MFMAs - and, across a tile boundary, the epilogue - to arrive in: the
+    // stage g & 1; chunks g + 1 .. g + kRtAhead are in flight from memory into a ring of registers (slot = chunk %
+    // kRtAhead), so a load has three chunks of MFMAs - and, across a tile boundary, the epilogue - to arrive in: the
     // candidate buffers leave room for ONE workgroup per CU, so no other wave hides a wait for memory.
     const int64_t total = (t_hi - t_lo) * n_k;
-    float ra[kFrAhead][8], rb[kFrAhead][4];
-    int64_t li0 = t_lo * kFrBM;                             // the next chunk to load: its tile's first item, its k
+    float ra[kRtAhead][8], rb[kRtAhead][4];
+    int64_t li0 = t_lo * kRtBM;                             // the next chunk to load: its tile's first item, its k
     int lk = 0;
     // No load sits behind a branch: an element outside the tables is read from the table's first element and zeroed
     // afterwards (Row::load_clamped's flavour), and chunks past the stream's end are issued like the others (their
@@ -184,22 +170,24 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
             row_load(Q, item, item < I, a + 4 * q);
         }
         row_load(P, my_uid, my_uid >= 0, b);
-        lk += kFrBK;
-        if (lk >= d) { lk = 0; li0 += kFrBM; }
+        lk += kRtBK;
+        if (lk >= d) { lk = 0; li0 += kRtBM; }
     };
     auto store = [&](int stage, const float (&a)[8], const float (&b)[4]) {
-        float *A = As + stage * kFrBK * kFrLA, *B = Bs + stage * kFrBK * kFrLB;
+        float *A = As + stage * kRtBK * kRtLA, *B = Bs + stage * kRtBK * kRtLB;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int x = 0; x < 4; ++x) A[(kk + x) * kFrLA + tid / 4 + q * 64] = a[4 * q + x];
+            for (int x = 0; x < 4; ++x) A[(kk + x) * kRtLA + tid / 4 + q * 64] = a[4 * q + x];
 #pragma unroll
-        for (int x = 0; x < 4; ++x) B[(kk + x) * kFrLB + tid / 4] = b[x];
+        for (int x = 0; x < 4; ++x) B[(kk + x) * kRtLB + tid / 4] = b[x];
     };
 
     floatx16 acc[2];
-    // lane holds user column (lane % 32) and items (i/4)*8 + (lane/32)*4 + i%4 of each 32x32 block: the C/D map
-    // gemm_epilogue decodes.  One step per mi: at most kFrStep words per user, then the full buffers are compacted.
+    // lane holds user column (lane % 32) and items rt_acc_item(i, lane) of each 32x32 block: the C/D map gemm_epilogue
+    // decodes.  One step per mi: at most kFrStep words per user, then the full buffers are compacted.  There is ONE
+    // mask buffer, which the next tile's build_mask overwrites: the __syncthreads_or below is the workgroup barrier that
+    // must follow the last mask read (k_frp_count, the second copy of this stream, has two buffers and no barrier).
     auto epilogue = [&](int64_t i0) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -213,11 +201,11 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
                 uint32_t pm = 0u;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int bit = (i / 4) * 8 + (lane / 32) * 4 + (i % 4);
+                    const int bit = rt_acc_item(i, lane);
                     const int64_t item = i0 + wm * 64 + mi * 32 + bit;
                     float v = acc[mi][i];
                     if (bu) v += (ep_bu + bi[item < I ? item : I - 1]) + ep_b0;
-                    w[i] = ((uint64_t)fr_key(v) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)item);
+                    w[i] = fr_word(v, item);
                     const bool pass = item < I && !((mw >> bit) & 1u) && w[i] > th;
                     pm |= pass ? (1u << i) : 0u;
                 }
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
                 }
             }
             if (__syncthreads_or(full)) {                   // some buffer could overflow in the next step
-                for (int u = wave; u < kFrBN; u += kBlock / kWave) {
+                for (int u = wave; u < kRtBN; u += kBlock / kWave) {
                     const int c = cnt[u];
                     if (c > kFrLimit)
                         fr_compact(buf + u * kFrBuf, c < kFrBuf ? c : kFrBuf, topk, lane, cnt + u, thr + u, nullptr);
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
         uint32_t m[4] = {0u, 0u, 0u, 0u};
         int64_t p = wc + wj;
         int64_t it = (int64_t)wv;
-        while (p < we && it < i0 + kFrBM) {
+        while (p < we && it < i0 + kRtBM) {
             if (it >= i0) {
                 const int b = (int)(it - i0);
 #pragma unroll
@@ -267,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
         uint64_t pm = (uint64_t)(p < we ? p : we);
 #pragma unroll
         for (int x = 1; x <= 2; x <<= 1) {
-            const uint64_t o = fr_shfl_xor(pm, x);
+            const uint64_t o = rt_shfl_xor(pm, x);
             pm = o < pm ? o : pm;
 #pragma unroll
             for (int q = 0; q < 4; ++q) m[q] |= (uint32_t)__shfl_xor((int)m[q], x, kWave);
@@ -278,16 +266,16 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
     };
 
 #pragma unroll
-    for (int j = 0; j < kFrAhead; ++j) issue(ra[j], rb[j]);
+    for (int j = 0; j < kRtAhead; ++j) issue(ra[j], rb[j]);
     store(0, ra[0], rb[0]);
     if (indptr) walk_fetch();
     else mask[tid] = 0u;
     __syncthreads();
     int stage = 0, kc = 0;
-    int64_t i0 = t_lo * kFrBM;
-    for (int64_t g0 = 0; g0 < total; g0 += kFrAhead) {
+    int64_t i0 = t_lo * kRtBM;
+    for (int64_t g0 = 0; g0 < total; g0 += kRtAhead) {
 #pragma unroll
-        for (int j = 0; j < kFrAhead; ++j) {
+        for (int j = 0; j < kRtAhead; ++j) {
             const int64_t g = g0 + j;
             if (g >= total) break;
             if (kc == 0) {
@@ -297,37 +285,37 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_tiles(
 #pragma unroll
                     for (int i = 0; i < 16; ++i) acc[mi][i] = 0.f;
             }
-            issue(ra[j], rb[j]);                    // chunk g + kFrAhead into chunk g's slot: g went to LDS an iteration ago
-            const float *as = As + stage * kFrBK * kFrLA + (lane / 32) * kFrLA + wm * 64 + lane % 32;
-            const float *bs = Bs + stage * kFrBK * kFrLB + (lane / 32) * kFrLB + wn * 32 + lane % 32;
+            issue(ra[j], rb[j]);                    // chunk g + kRtAhead into chunk g's slot: g went to LDS an iteration ago
+            const float *as = As + stage * kRtBK * kRtLA + (lane / 32) * kRtLA + wm * 64 + lane % 32;
+            const float *bs = Bs + stage * kRtBK * kRtLB + (lane / 32) * kRtLB + wn * 32 + lane % 32;
             float a[2][2], b[2];
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) a[0][mi] = as[mi * 32];
             b[0] = bs[0];
 #pragma unroll
-            for (int ks = 0; ks < kFrBK / 2; ++ks) {
+            for (int ks = 0; ks < kRtBK / 2; ++ks) {
                 const int c = ks & 1, nx = c ^ 1;
-                if (ks + 1 < kFrBK / 2) {
+                if (ks + 1 < kRtBK / 2) {
 #pragma unroll
-                    for (int mi = 0; mi < 2; ++mi) a[nx][mi] = as[(2 * ks + 2) * kFrLA + mi * 32];
-                    b[nx] = bs[(2 * ks + 2) * kFrLB];
+                    for (int mi = 0; mi < 2; ++mi) a[nx][mi] = as[(2 * ks + 2) * kRtLA + mi * 32];
+                    b[nx] = bs[(2 * ks + 2) * kRtLB];
                 }
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
                     acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][mi], b[c], acc[mi], 0, 0, 0);
             }
-            if (g + 1 < total) store(stage ^ 1, ra[(j + 1) % kFrAhead], rb[(j + 1) % kFrAhead]);
+            if (g + 1 < total) store(stage ^ 1, ra[(j + 1) % kRtAhead], rb[(j + 1) % kRtAhead]);
             __syncthreads();
             stage ^= 1;
             if (++kc == n_k) {
                 kc = 0;
                 epilogue(i0);
-                i0 += kFrBM;
+                i0 += kRtBM;
             }
         }
     }
 
-    for (int u = wave; u < kFrBN; u += kBlock / kWave) {
+    for (int u = wave; u < kRtBN; u += kBlock / kWave) {
         if (uid[u] < 0) continue;
         const int c = cnt[u];
         fr_compact(buf + u * kFrBuf, c < kFrBuf ? c : kFrBuf, topk, lane, nullptr, nullptr,
@@ -366,21 +354,9 @@ __global__ __launch_bounds__(kBlock) void k_full_rank_merge(const uint64_t *__re
         const int e = lane * 4 + r;
         if (e >= topk) continue;
         const bool none = w[r] == 0ull;
-        ids[u * topk + e] = none ? (int64_t)-1 : (int64_t)(0xFFFFFFFFu - (uint32_t)w[r]);
-        if (scores) scores[u * topk + e] = none ? -INFINITY : fr_unkey((uint32_t)(w[r] >> 32));
+        ids[u * topk + e] = none ? (int64_t)-1 : fr_word_item(w[r]);
+        if (scores) scores[u * topk + e] = none ? -INFINITY : fr_word_score(w[r]);
     }
-}
-
-// item slices of a call: whole 128-item tiles, every slice non-empty.  requested 0: as many as bring the grid to about
-// kFrTargetGroups workgroups (one workgroup per CU is resident: its candidate buffers take most of the LDS).
-static void fr_slices(int64_t n, int64_t item_num, int32_t requested, int64_t *tiles_per_slice, int64_t *n_tiles, int *S) {
-    const int64_t T = (item_num + kFrBM - 1) / kFrBM, UT = (n + kFrBN - 1) / kFrBN;
-    int64_t want = requested > 0 ? requested : (kFrTargetGroups / UT > 1 ? kFrTargetGroups / UT : 1);
-    if (want > T) want = T;
-    const int64_t per = (T + want - 1) / want;
-    *tiles_per_slice = per;
-    *n_tiles = T;
-    *S = (int)((T + per - 1) / per);
 }
 
 }  // namespace daisy
@@ -395,7 +371,7 @@ size_t daisy_full_rank_users_workspace_bytes(int64_t n, int64_t item_num, int32_
         return 0;
     int64_t per, T;
     int S;
-    fr_slices(n, item_num, item_slices, &per, &T, &S);
+    rt_slices(n, item_num, item_slices, kFrTargetGroups, &per, &T, &S);
     return align_up((size_t)n * (size_t)S * (size_t)topk * 8);
 }
 
@@ -421,13 +397,12 @@ int daisy_full_rank_users(const float *P, const float *Q, const float *u_bias, c
                     "full_rank_users: workspace too small");
     int64_t per, T;
     int S;
-    fr_slices(n, item_num, item_slices, &per, &T, &S);
+    rt_slices(n, item_num, item_slices, kFrTargetGroups, &per, &T, &S);
     hipStream_t s = as_stream(stream);
-    const bool vec = (d % 4 == 0) && (reinterpret_cast<uintptr_t>(P) % 16 == 0) && (reinterpret_cast<uintptr_t>(Q) % 16 == 0);
-    auto kern = vec ? k_full_rank_tiles<true> : k_full_rank_tiles<false>;      // float4 rows, or element by element
+    auto kern = rt_vec(d, P, Q) ? k_full_rank_tiles<true> : k_full_rank_tiles<false>;      // float4 rows, or element by element
     DAISY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kFrLdsBytes));
     uint64_t *part = static_cast<uint64_t *>(workspace);
-    const int64_t UT = (n + kFrBN - 1) / kFrBN;
+    const int64_t UT = (n + kRtBN - 1) / kRtBN;
     hipLaunchKernelGGL(kern, dim3((unsigned)UT, (unsigned)S), dim3(kBlock), kFrLdsBytes, s, P, Q, u_bias, i_bias,
                        bias, (int)d, item_num, users, n, excl_indptr, excl_items, (int)topk, per, T, S, part);
     DAISY_LAUNCH_CHECK();

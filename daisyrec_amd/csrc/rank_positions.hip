@@ -15,29 +15,18 @@
 #include "common.h"
 #include "mfma.h"
 #include "rank_key_f32.h"
+#include "rank_tiles_f32.h"                     // the kRt* tile and the helpers shared with k_full_rank_tiles
 
 namespace daisy {
 
-constexpr int kFrpBM = 128;                     // items per tile (MFMA M side)
-constexpr int kFrpBN = 64;                      // slots per tile (MFMA N side)
-constexpr int kFrpBK = 16;                      // k depth of an LDS tile
-constexpr int kFrpLA = kFrpBM + 4, kFrpLB = kFrpBN + 4;
 constexpr int kFrpTc = 32;                      // targets of a slot: one MFMA block of pass 1, one LDS row of pass 2
-constexpr int kFrpAhead = 4;                    // chunks in flight from memory ahead of the one in LDS
 constexpr int kFrpTargetGroups = 1024;          // item slices are added until the grid has about this many workgroups
 constexpr uint64_t kFrpNone = ~0ull;            // the word of a target that is not ranked: no word is larger
 
 // LDS of k_frp_count: target words and counts [kFrpTc][64] (slot fastest: the lanes of a wave read neighbouring
 // banks), the operand stages, two exclusion masks (tile t uses mask t & 1: the epilogue needs no barrier), and per slot
 // the exclusion cursor, row end, user id, first output index and target count
-constexpr int kFrpLdsBytes = kFrpTc * kFrpBN * (8 + 4) + 2 * kFrpBK * (kFrpLA + kFrpLB) * 4 + 2 * kFrpBN * 4 * 4 +
-                             kFrpBN * (4 * 8 + 4);
-
-__device__ __forceinline__ uint64_t frp_shfl_xor(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, kWave);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, kWave);
-    return ((uint64_t)hi << 32) | lo;
-}
+constexpr int kFrpLdsBytes = kFrpTc * kRtBN * (8 + 4) + kRtStageBytes + 2 * kRtMaskBytes + kRtBN * (4 * 8 + 4);
 
 // slots of request b: its target row in blocks of kFrpTc, at least one (the eligible count has to come from somewhere)
 __device__ __forceinline__ int64_t frp_slots_of(const int64_t *__restrict__ users, const int64_t *__restrict__ t_indptr,
@@ -127,19 +116,14 @@ __global__ __launch_bounds__(kBlock) void k_frp_targets(
     const bool in_range = tgt >= 0 && tgt < I;
     bool excluded = false;
     if (indptr && in_range) {                               // row contents are only compared
-        int64_t a = indptr[u], e = indptr[u + 1];
-        const int64_t hi = e;
-        while (a < e) {
-            const int64_t m = a + (e - a) / 2;
-            if ((int64_t)eitems[m] < tgt) a = m + 1;
-            else e = m;
-        }
+        const int64_t hi = indptr[u + 1];
+        const int64_t a = rt_lower_bound(eitems, indptr[u], hi, tgt);
         excluded = a < hi && (int64_t)eitems[a] == tgt;
     }
     floatx16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int k_end = (d + kFrpBK - 1) / kFrpBK * kFrpBK;
+    const int k_end = (d + kRtBK - 1) / kRtBK * kRtBK;
     for (int k0 = 0; k0 < k_end; k0 += 2) {
         const int k = k0 + kh;
         const bool ka = in_range && k < d, kb = r == 0 && k < d;
@@ -150,21 +134,24 @@ __global__ __launch_bounds__(kBlock) void k_frp_targets(
     if (bu) { ep_bu = bu[u]; ep_b0 = b0[0]; }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int row = (i / 4) * 8 + kh * 4 + (i % 4);
+        const int row = rt_acc_item(i, lane);
         const int64_t item = __shfl((long long)tgt, row, kWave);        // every lane takes part in the exchange
         const bool ok = __shfl((int)(in_range && !excluded), row, kWave) != 0;
         if (r != 0 || row >= len || dst0 + row >= T) continue;
         float v = acc[i];
         if (bu && ok) v += (ep_bu + bi[item]) + ep_b0;
-        const uint32_t key = fr_key(v);
-        words[dst0 + row] = ok ? (((uint64_t)key << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)item)) : kFrpNone;
+        const uint64_t word = fr_word(v, item);
+        words[dst0 + row] = ok ? word : kFrpNone;
         out_pos[dst0 + row] = ok ? 0 : -1;
-        if (out_scores) out_scores[dst0 + row] = ok ? fr_unkey(key) : -INFINITY;
+        if (out_scores) out_scores[dst0 + row] = ok ? fr_word_score(word) : -INFINITY;
     }
 }
 
 // Pass 2.  The tile loop, the chunk stream and the exclusion walk are k_full_rank_tiles' (rank_full.hip explains them);
-// "user" there is "slot" here.
+// "user" there is "slot" here.  They are a second copy on purpose (rank_tiles_f32.h says what the shared forms cost): a
+// change to the loop in one file belongs in the other too.  The one difference is the mask: two buffers here (tile t
+// uses t & 1), so this epilogue needs no barrier; one buffer there, so that epilogue must have a workgroup barrier
+// after its last mask read (its __syncthreads_or).
 template <bool VEC>
 __global__ __launch_bounds__(kBlock) void k_frp_count(
     const float *__restrict__ P, const float *__restrict__ Q, const float *__restrict__ bu, const float *__restrict__ bi,
@@ -175,24 +162,24 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
     int32_t *__restrict__ out_eligible) {
     extern __shared__ __attribute__((aligned(16))) unsigned char frp_lds[];
     uint64_t *tw = reinterpret_cast<uint64_t *>(frp_lds);                       // [kFrpTc][64] target words
-    int64_t *cur = reinterpret_cast<int64_t *>(tw + kFrpTc * kFrpBN);           // [64] the slice's first exclusion cursor
-    int64_t *end = cur + kFrpBN;                                                // [64] the exclusion row's end
-    int64_t *uid = end + kFrpBN;                                                // [64] user id of the slot, -1: empty
-    int64_t *dst = uid + kFrpBN;                                                // [64] first index into out_pos
-    float *As = reinterpret_cast<float *>(dst + kFrpBN);                        // [2][kFrpBK * kFrpLA]
-    float *Bs = As + 2 * kFrpBK * kFrpLA;                                       // [2][kFrpBK * kFrpLB]
-    uint32_t *mask = reinterpret_cast<uint32_t *>(Bs + 2 * kFrpBK * kFrpLB);    // [2][64][4]: bit = item of the tile
-    int *cnt = reinterpret_cast<int *>(mask + 2 * kFrpBN * 4);                  // [kFrpTc][64] words above the target
-    int *nt = cnt + kFrpTc * kFrpBN;                                            // [64] targets of the slot
+    int64_t *cur = reinterpret_cast<int64_t *>(tw + kFrpTc * kRtBN);           // [64] the slice's first exclusion cursor
+    int64_t *end = cur + kRtBN;                                                // [64] the exclusion row's end
+    int64_t *uid = end + kRtBN;                                                // [64] user id of the slot, -1: empty
+    int64_t *dst = uid + kRtBN;                                                // [64] first index into out_pos
+    float *As = reinterpret_cast<float *>(dst + kRtBN);                        // [2][kRtBK * kRtLA]
+    float *Bs = As + 2 * kRtBK * kRtLA;                                       // [2][kRtBK * kRtLB]
+    uint32_t *mask = reinterpret_cast<uint32_t *>(Bs + 2 * kRtBK * kRtLB);    // [2][64][4]: bit = item of the tile
+    int *cnt = reinterpret_cast<int *>(mask + 2 * kRtBN * 4);                  // [kFrpTc][64] words above the target
+    int *nt = cnt + kFrpTc * kRtBN;                                            // [64] targets of the slot
 
     const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
     const int wm = wave / 2, wn = wave % 2;
-    const int64_t s0 = (int64_t)blockIdx.x * kFrpBN;
+    const int64_t s0 = (int64_t)blockIdx.x * kRtBN;
     const int64_t t_lo = (int64_t)blockIdx.y * tiles_per_slice;
     const int64_t t_hi = (t_lo + tiles_per_slice < n_tiles) ? (t_lo + tiles_per_slice) : n_tiles;
 
     bool counts_eligible = false;                           // tid < 64: the slot is the first of its request
-    if (tid < kFrpBN) {
+    if (tid < kRtBN) {
         const int64_t slot = s0 + tid;
         const int64_t b = (slot < n_slots) ? slot_req[slot] : -1;
         int64_t u = -1, lo = 0, hi = 0, d0 = 0;
@@ -206,16 +193,8 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
             if (d0 + c > T) c = (int)(T > d0 ? T - d0 : 0);  // (never, when out_indptr is the prefix sum of the rows)
             counts_eligible = off == 0;
             if (indptr) {
-                lo = indptr[u];
                 hi = indptr[u + 1];
-                const int64_t first = t_lo * kFrpBM;
-                int64_t a = lo, e = hi;
-                while (a < e) {
-                    const int64_t m = a + (e - a) / 2;
-                    if ((int64_t)eitems[m] < first) a = m + 1;
-                    else e = m;
-                }
-                lo = a;
+                lo = rt_lower_bound(eitems, indptr[u], hi, t_lo * kRtBM);   // the slice's first item
             }
         }
         uid[tid] = u;
@@ -224,9 +203,9 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
         dst[tid] = d0;
         nt[tid] = c;
     }
-    if (__syncthreads_count(tid < kFrpBN && uid[tid] >= 0) == 0) return;        // a tile past the last slot
-    for (int idx = tid; idx < kFrpTc * kFrpBN; idx += kBlock) {
-        const int t = idx / kFrpBN, sl = idx % kFrpBN;
+    if (__syncthreads_count(tid < kRtBN && uid[tid] >= 0) == 0) return;        // a tile past the last slot
+    for (int idx = tid; idx < kFrpTc * kRtBN; idx += kBlock) {
+        const int t = idx / kRtBN, sl = idx % kRtBN;
         tw[idx] = (t < nt[sl]) ? words[dst[sl] + t] : kFrpNone;
         cnt[idx] = 0;
     }
@@ -241,17 +220,17 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
     const int ep_nt = nt[ul];
     uint64_t ep_min = kFrpNone;                             // the slot's smallest target word: most values lie below it
     for (int t = 0; t < ep_nt; ++t) {
-        const uint64_t x = tw[t * kFrpBN + ul];
+        const uint64_t x = tw[t * kRtBN + ul];
         ep_min = x < ep_min ? x : ep_min;
     }
     float ep_bu = 0.f, ep_b0 = 0.f;
     if (bu && ep_uid >= 0) { ep_bu = bu[ep_uid]; ep_b0 = b0[0]; }
     int elig = 0;                                           // tid < 64: eligible items of slot tid in this slice
     const int kk = (tid % 4) * 4;
-    const int n_k = (d + kFrpBK - 1) / kFrpBK;
+    const int n_k = (d + kRtBK - 1) / kRtBK;
     const int64_t total = (t_hi - t_lo) * n_k;
-    float ra[kFrpAhead][8], rb[kFrpAhead][4];
-    int64_t li0 = t_lo * kFrpBM;
+    float ra[kRtAhead][8], rb[kRtAhead][4];
+    int64_t li0 = t_lo * kRtBM;
     int lk = 0;
     // no load sits behind a branch: an element outside the tables is read from the table's first element and zeroed
     auto issue = [&](float (&a)[8], float (&b)[4]) {
@@ -276,17 +255,17 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
             row_load(Q, item, item < I, a + 4 * q);
         }
         row_load(P, my_uid, my_uid >= 0, b);
-        lk += kFrpBK;
-        if (lk >= d) { lk = 0; li0 += kFrpBM; }
+        lk += kRtBK;
+        if (lk >= d) { lk = 0; li0 += kRtBM; }
     };
     auto store = [&](int stage, const float (&a)[8], const float (&b)[4]) {
-        float *A = As + stage * kFrpBK * kFrpLA, *B = Bs + stage * kFrpBK * kFrpLB;
+        float *A = As + stage * kRtBK * kRtLA, *B = Bs + stage * kRtBK * kRtLB;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int x = 0; x < 4; ++x) A[(kk + x) * kFrpLA + tid / 4 + q * 64] = a[4 * q + x];
+            for (int x = 0; x < 4; ++x) A[(kk + x) * kRtLA + tid / 4 + q * 64] = a[4 * q + x];
 #pragma unroll
-        for (int x = 0; x < 4; ++x) B[(kk + x) * kFrpLB + tid / 4] = b[x];
+        for (int x = 0; x < 4; ++x) B[(kk + x) * kRtLB + tid / 4] = b[x];
     };
 
     floatx16 acc[2];
@@ -300,21 +279,22 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
             bool any = false;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int bit = (i / 4) * 8 + (lane / 32) * 4 + (i % 4);
+                const int bit = rt_acc_item(i, lane);
                 const int64_t item = i0 + wm * 64 + mi * 32 + bit;
                 float v = acc[mi][i];
                 if (bu) v += (ep_bu + bi[item < I ? item : I - 1]) + ep_b0;
+                // (fr_word, written out: through the helper this kernel came out 26 VGPRs larger, at one wave per SIMD)
                 const uint64_t word = ((uint64_t)fr_key(v) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)item);
                 w[i] = (item < I && !((mw >> bit) & 1u)) ? word : 0ull;        // 0: above no target
                 any |= w[i] > ep_min;
             }
             if (any) {
                 for (int t = 0; t < ep_nt; ++t) {
-                    const uint64_t x = tw[t * kFrpBN + ul];
+                    const uint64_t x = tw[t * kRtBN + ul];
                     int c = 0;
 #pragma unroll
                     for (int i = 0; i < 16; ++i) c += (w[i] > x) ? 1 : 0;
-                    if (c) atomicAdd(&cnt[t * kFrpBN + ul], c);
+                    if (c) atomicAdd(&cnt[t * kRtBN + ul], c);
                 }
             }
         }
@@ -325,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
         uint32_t m[4] = {0u, 0u, 0u, 0u};
         int64_t p = wc + wj;
         int64_t it = (int64_t)wv;
-        while (p < we && it < i0 + kFrpBM) {
+        while (p < we && it < i0 + kRtBM) {
             if (it >= i0) {
                 const int b = (int)(it - i0);
 #pragma unroll
@@ -337,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
         uint64_t pm = (uint64_t)(p < we ? p : we);
 #pragma unroll
         for (int x = 1; x <= 2; x <<= 1) {
-            const uint64_t o = frp_shfl_xor(pm, x);
+            const uint64_t o = rt_shfl_xor(pm, x);
             pm = o < pm ? o : pm;
 #pragma unroll
             for (int q = 0; q < 4; ++q) m[q] |= (uint32_t)__shfl_xor((int)m[q], x, kWave);
@@ -348,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
     };
     // eligible items of slot tid in the tile at i0: the tile's items below I without the mask's bits
     auto count_eligible = [&](int64_t i0, const uint32_t *__restrict__ mk) {
-        if (tid >= kFrpBN) return;
+        if (tid >= kRtBN) return;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int64_t left = I - (i0 + q * 32);         // items of this word that exist
@@ -358,16 +338,16 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
     };
 
 #pragma unroll
-    for (int j = 0; j < kFrpAhead; ++j) issue(ra[j], rb[j]);
+    for (int j = 0; j < kRtAhead; ++j) issue(ra[j], rb[j]);
     store(0, ra[0], rb[0]);
     if (indptr) walk_fetch();
     else { mask[tid] = 0u; mask[kBlock + tid] = 0u; }
     __syncthreads();
     int stage = 0, kc = 0, mb = 0;
-    int64_t i0 = t_lo * kFrpBM;
-    for (int64_t g0 = 0; g0 < total; g0 += kFrpAhead) {
+    int64_t i0 = t_lo * kRtBM;
+    for (int64_t g0 = 0; g0 < total; g0 += kRtAhead) {
 #pragma unroll
-        for (int j = 0; j < kFrpAhead; ++j) {
+        for (int j = 0; j < kRtAhead; ++j) {
             const int64_t g = g0 + j;
             if (g >= total) break;
             if (kc == 0) {
@@ -378,56 +358,44 @@ __global__ __launch_bounds__(kBlock) void k_frp_count(
                     for (int i = 0; i < 16; ++i) acc[mi][i] = 0.f;
             }
             issue(ra[j], rb[j]);
-            const float *as = As + stage * kFrpBK * kFrpLA + (lane / 32) * kFrpLA + wm * 64 + lane % 32;
-            const float *bs = Bs + stage * kFrpBK * kFrpLB + (lane / 32) * kFrpLB + wn * 32 + lane % 32;
+            const float *as = As + stage * kRtBK * kRtLA + (lane / 32) * kRtLA + wm * 64 + lane % 32;
+            const float *bs = Bs + stage * kRtBK * kRtLB + (lane / 32) * kRtLB + wn * 32 + lane % 32;
             float a[2][2], b[2];
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) a[0][mi] = as[mi * 32];
             b[0] = bs[0];
 #pragma unroll
-            for (int ks = 0; ks < kFrpBK / 2; ++ks) {
+            for (int ks = 0; ks < kRtBK / 2; ++ks) {
                 const int c = ks & 1, nx = c ^ 1;
-                if (ks + 1 < kFrpBK / 2) {
+                if (ks + 1 < kRtBK / 2) {
 #pragma unroll
-                    for (int mi = 0; mi < 2; ++mi) a[nx][mi] = as[(2 * ks + 2) * kFrpLA + mi * 32];
-                    b[nx] = bs[(2 * ks + 2) * kFrpLB];
+                    for (int mi = 0; mi < 2; ++mi) a[nx][mi] = as[(2 * ks + 2) * kRtLA + mi * 32];
+                    b[nx] = bs[(2 * ks + 2) * kRtLB];
                 }
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
                     acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][mi], b[c], acc[mi], 0, 0, 0);
             }
-            if (g + 1 < total) store(stage ^ 1, ra[(j + 1) % kFrpAhead], rb[(j + 1) % kFrpAhead]);
+            if (g + 1 < total) store(stage ^ 1, ra[(j + 1) % kRtAhead], rb[(j + 1) % kRtAhead]);
             __syncthreads();                                // (the tile's mask is complete here as well)
             stage ^= 1;
             if (++kc == n_k) {
                 kc = 0;
                 count_eligible(i0, mask + mb * kBlock);
                 epilogue(i0, mask + mb * kBlock);
-                i0 += kFrpBM;
+                i0 += kRtBM;
                 mb ^= 1;
             }
         }
     }
 
     __syncthreads();
-    for (int idx = tid; idx < kFrpTc * kFrpBN; idx += kBlock) {
-        const int t = idx / kFrpBN, sl = idx % kFrpBN;
+    for (int idx = tid; idx < kFrpTc * kRtBN; idx += kBlock) {
+        const int t = idx / kRtBN, sl = idx % kRtBN;
         const int c = cnt[idx];
         if (c && t < nt[sl]) atomicAdd(&out_pos[dst[sl] + t], c);       // (a target that is not ranked counted nothing)
     }
-    if (out_eligible && tid < kFrpBN && counts_eligible && elig) atomicAdd(&out_eligible[slot_req[s0 + tid]], elig);
-}
-
-// item slices of a call: whole 128-item tiles, every slice non-empty.  requested 0: as many as bring the grid to about
-// kFrpTargetGroups workgroups.
-static void frp_slices(int64_t n_slots, int64_t item_num, int32_t requested, int64_t *tiles_per_slice, int64_t *n_tiles, int *S) {
-    const int64_t T = (item_num + kFrpBM - 1) / kFrpBM, UT = (n_slots + kFrpBN - 1) / kFrpBN;
-    int64_t want = requested > 0 ? requested : (kFrpTargetGroups / UT > 1 ? kFrpTargetGroups / UT : 1);
-    if (want > T) want = T;
-    const int64_t per = (T + want - 1) / want;
-    *tiles_per_slice = per;
-    *n_tiles = T;
-    *S = (int)((T + per - 1) / per);
+    if (out_eligible && tid < kRtBN && counts_eligible && elig) atomicAdd(&out_eligible[slot_req[s0 + tid]], elig);
 }
 
 struct FrpLayout {
@@ -489,10 +457,9 @@ int daisy_full_rank_positions(const float *P, const float *Q, const float *u_bia
     int64_t *bsum = reinterpret_cast<int64_t *>(ws + lay.bsum);
     int64_t per, n_tiles;
     int S;
-    frp_slices(lay.n_slots, item_num, item_slices, &per, &n_tiles, &S);
+    rt_slices(lay.n_slots, item_num, item_slices, kFrpTargetGroups, &per, &n_tiles, &S);
     hipStream_t s = as_stream(stream);
-    const bool vec = (d % 4 == 0) && (reinterpret_cast<uintptr_t>(P) % 16 == 0) && (reinterpret_cast<uintptr_t>(Q) % 16 == 0);
-    auto kern = vec ? k_frp_count<true> : k_frp_count<false>;
+    auto kern = rt_vec(d, P, Q) ? k_frp_count<true> : k_frp_count<false>;
     DAISY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kFrpLdsBytes));
 
     DAISY_HIP(hipMemsetAsync(slot_req, 0xFF, (size_t)lay.n_slots * 8, s));      // -1: a slot no request fills
@@ -511,7 +478,7 @@ int daisy_full_rank_positions(const float *P, const float *Q, const float *u_bia
                            words, out_pos, out_scores);
         DAISY_LAUNCH_CHECK();
     }
-    const int64_t UT = (lay.n_slots + kFrpBN - 1) / kFrpBN;
+    const int64_t UT = (lay.n_slots + kRtBN - 1) / kRtBN;
     hipLaunchKernelGGL(kern, dim3((unsigned)UT, (unsigned)S), block, kFrpLdsBytes, s, P, Q, u_bias, i_bias, bias, (int)d,
                        item_num, users, excl_indptr, excl_items, t_indptr, out_indptr, n_targets, slot_req, slot_off,
                        lay.n_slots, per, n_tiles, words, out_pos, out_eligible);

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_rows_f32(const float *__restric
             int tot = 0;
 #pragma unroll
             for (int x = 0; x < kRrPer; ++x) {
-                w[x] = ((uint64_t)fr_key(v[x]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(i0 + x));
+                w[x] = fr_word(v[x], i0 + x);
                 bal[x] = __ballot(((pre >> x) & 1u) && w[x] > thr);
                 tot += __popcll(bal[x]);
             }
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_rows_f32(const float *__restric
             const int c = n < kRrBuf ? n : kRrBuf;
             rr_sort(st, c);
             thr = (c >= topk) ? st.word[topk - 1] : 0ull;
-            thr_f = thr ? fr_unkey((uint32_t)(thr >> 32)) : -INFINITY;
+            thr_f = thr ? fr_word_score(thr) : -INFINITY;
             if (tid == 0) st.cnt = c < topk ? c : topk;
             __syncthreads();
         }
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_rows_f32(const float *__restric
     if (c > 1) rr_sort(st, c);                              // (uniform)
     if (tid < topk) {
         const bool has = tid < c;
-        const int64_t id = has ? (int64_t)(0xFFFFFFFFu - (uint32_t)st.word[has ? tid : 0]) : (int64_t)-1;
+        const int64_t id = has ? fr_word_item(st.word[has ? tid : 0]) : (int64_t)-1;
         out_ids[r * topk + tid] = id;
         // the row's own stored value, not the key decoded: the bits of the score kernel (a NaN's payload, the sign of a zero)
         if (out_scores) out_scores[r * topk + tid] = has ? row[id] : -INFINITY;

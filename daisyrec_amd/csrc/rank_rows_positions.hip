@@ -33,10 +33,6 @@ struct RrpState {
     uint32_t mask[2][kRrpStep / 32];               // step s uses mask s & 1: a step needs no closing barrier
 };
 
-__device__ __forceinline__ uint64_t rrp_word(float v, int64_t item) {
-    return ((uint64_t)fr_key(v) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)item);
-}
-
 // VEC: scores is 16-byte aligned and pitch % 4 == 0, so a thread's four items of a whole step are one float4
 template <bool VEC>
 __global__ __launch_bounds__(kBlock) void k_rank_rows_positions_f32(
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_rows_positions_f32(
                 }
                 if (ok) {
                     mine_s[q] = row[t];                     // the row's own stored value, with its bits
-                    mine[q] = rrp_word(mine_s[q], t);
+                    mine[q] = fr_word(mine_s[q], t);
                     st.rc.tgt[atomicAdd(&st.rc.cnt, 1)] = mine[q];          // (at most len <= kRcTc entries)
                 }
             }
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_rows_positions_f32(
 #pragma unroll
             for (int x = 0; x < kRrpPer; ++x) {             // four independent searches
                 on[x] = i0 + x < I && !((ex >> x) & 1u);
-                g[x] = on[x] ? rc_before_count<RrpOrd>(st.rc.tgt, c, rrp_word(v[x], i0 + x)) : 0;
+                g[x] = on[x] ? rc_before_count<RrpOrd>(st.rc.tgt, c, fr_word(v[x], i0 + x)) : 0;
             }
             if (c < kRcFew) {                               // (uniform)
                 rc_bucket_add_few<kRrpPer>(st.rc.bucket, on, g, c);
