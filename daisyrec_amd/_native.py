@@ -48,6 +48,16 @@ class NeumfParams(C.Structure):
 
 _pp = C.POINTER(NeumfParams)
 
+SMALL_TRIAL_WS_BYTES = 192
+
+
+class SmallTrial(C.Structure):
+    """daisy_small_trial: one model of daisy_bpr_fit_epoch_sgd_many (include/daisyrec_amd.h)."""
+    _fields_ = [("ctx", _p), ("plan", _p), ("P", _p), ("Q", _p), ("loss_type", C.c_int32), ("gamma", C.c_float),
+                ("lr", C.c_float), ("reg_1", C.c_float), ("reg_2", C.c_float),
+                ("stats", _p), ("epoch_acc", _p), ("step_losses", _p)]
+
+
 GEMM_LAUNCH, GEMM_LAUNCH_H, GEMM_LAUNCH_PAIR = 0, 1, 2
 GEMM_EPI_STORE, GEMM_EPI_BIAS_RELU, GEMM_EPI_GATE, GEMM_EPI_ATOMIC = 0, 1, 2, 3
 GEMM_F32, GEMM_BF16IN, GEMM_H, GEMM_PAIR = 0, 1, 2, 3          # kernel family in daisy_gemm_desc.path
@@ -180,6 +190,7 @@ SIGNATURES = {
     "daisy_bpr_fit_epoch_adam": (C.c_int, [_p, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _p, _p, _p, _p, _i64,
                                            _f32, _f32, _f32, _i64, _i32, _p, _p, _p, _p]),
     "daisy_bpr_small_epoch_supported": (C.c_int, [_p, _p, _i32]),
+    "daisy_bpr_fit_epoch_sgd_many": (C.c_int, [C.POINTER(SmallTrial), _i32, _p, _sz, _p]),
     "daisy_mf_predict": (C.c_int, [_p, _p, _i32, _p, _p, _i64, _p, _p]),
     "daisy_mf_rank_workspace_bytes": (_sz, [_i64, _i64]),
     "daisy_mf_rank_topk": (C.c_int, [_p, _p, _i32, _p, _p, _i64, _i64, _i32, _p, _p, _p, _sz, _p]),

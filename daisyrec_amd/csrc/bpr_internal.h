@@ -75,6 +75,9 @@ struct SmallAdamArgs {
 int small_fit_epoch(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, float *P, float *Q, int loss_type, float gamma,
                     float lr, float reg_1, float reg_2, double *stats, double *epoch_acc, double *step_losses,
                     hipStream_t s, const SmallAdamArgs *adam = nullptr);
+// one SGD epoch of `count` independent models, one workgroup each (daisy_bpr_fit_epoch_sgd_many): every trial must pass
+// small_epoch_supported, no two may share what they write; `workspace` (device) carries the per-trial argument records
+int small_fit_epoch_many(const daisy_small_trial *trials, int count, void *workspace, size_t workspace_bytes, hipStream_t s);
 // bpr_train.hip: fixed-order reduction of `nblocks` x 8 per-workgroup sums into stats[0..6,12]; finalize: also
 // the norms and the loss (finalize_stats)
 int launch_reduce_partials(const double *partials, int nblocks, double *stats, bool finalize, float reg_1,

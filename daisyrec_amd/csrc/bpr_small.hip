@@ -26,6 +26,10 @@
 // in bpr_train.hip only comes here for B <= kSmallBatchMax and rows that fit the LDS).
 #include <stdlib.h>
 
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "bpr_internal.h"
 
 namespace daisy {
@@ -178,11 +182,14 @@ __device__ void small_adam_helper(float *__restrict__ P, float *__restrict__ Q, 
     }
 }
 
-template <class C, int MODE, bool ADAM = false>      // rows staged in LDS per sample: 3 = q_i, q_j, p_u; 2 = q_i, q_j; 1 = p_u only
-__global__ __launch_bounds__(kSmallThreads) void k_small_epoch(
-    float *__restrict__ P, float *__restrict__ Q, SmallPlan pl, int d, int dpad, int loss_type, float gamma, float lr,
+// The epoch of ONE model on ONE workgroup: the body of both kernels below (k_small_epoch: one model per launch;
+// k_small_epoch_many: one model per workgroup of the grid).  Called by all kSmallThreads threads of the workgroup with
+// uniform arguments; the LDS arrays declared here belong to the calling kernel.
+template <class C, int MODE, bool ADAM>      // rows staged in LDS per sample: 3 = q_i, q_j, p_u; 2 = q_i, q_j; 1 = p_u only
+__device__ __forceinline__ void small_epoch_body(
+    float *__restrict__ P, float *__restrict__ Q, const SmallPlan &pl, int d, int dpad, int loss_type, float gamma, float lr,
     float reg_1, float reg_2, double *__restrict__ stats, double *__restrict__ epoch_acc,
-    double *__restrict__ step_losses, SmallAdam ad = SmallAdam{}) {
+    double *__restrict__ step_losses, const SmallAdam &ad) {
     constexpr int G = kSmallThreads / C::LPR;
     constexpr int NW = kSmallThreads / kWave;
     constexpr int UN = (C::NE <= 4) ? 2 : 1;            // samples whose 3 row gathers are issued together per lane group
@@ -487,6 +494,35 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_epoch(
     if (tid == 0 && epoch_acc) { epoch_acc[0] += acc_epoch; epoch_acc[1] += nan_epoch; }
 }
 
+template <class C, int MODE, bool ADAM = false>
+__global__ __launch_bounds__(kSmallThreads) void k_small_epoch(
+    float *__restrict__ P, float *__restrict__ Q, SmallPlan pl, int d, int dpad, int loss_type, float gamma, float lr,
+    float reg_1, float reg_2, double *__restrict__ stats, double *__restrict__ epoch_acc,
+    double *__restrict__ step_losses, SmallAdam ad = SmallAdam{}) {
+    small_epoch_body<C, MODE, ADAM>(P, Q, pl, d, dpad, loss_type, gamma, lr, reg_1, reg_2, stats, epoch_acc, step_losses, ad);
+}
+
+// ---- many models per launch (a hyper-parameter search, the folds of a cross-validation) -----------------------------
+// The SGD epoch above never looks beyond its own workgroup: N independent models are N workgroups of one launch, each
+// running the body on the argument record of its own model.  There is no wait on another workgroup anywhere on this path
+// (which is why the lazy-Adam form, whose main workgroup waits for helpers, stays out of it): a grid larger than the
+// number of CUs simply queues.
+struct SmallTrial {          // what k_small_epoch takes as kernel arguments, per model
+    float *P, *Q;
+    SmallPlan pl;
+    int d, dpad, loss_type;
+    float gamma, lr, reg_1, reg_2;
+    double *stats, *epoch_acc, *step_losses;
+};
+static_assert(sizeof(SmallTrial) <= DAISY_SMALL_TRIAL_WS_BYTES, "the header promises callers this much workspace per trial");
+
+template <class C, int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_epoch_many(const SmallTrial *__restrict__ trials) {
+    const SmallTrial t = trials[blockIdx.x];           // a uniform address: the record arrives through scalar loads, once
+    small_epoch_body<C, MODE, false>(t.P, t.Q, t.pl, t.d, t.dpad, t.loss_type, t.gamma, t.lr, t.reg_1, t.reg_2, t.stats,
+                                     t.epoch_acc, t.step_losses, SmallAdam{});
+}
+
 // floats per staged row: float4-aligned; rows that are a multiple of 128 bytes get one float4 of padding when three
 // row sets still fit (every row would start on the same banks otherwise: measured 11.3 vs 7.x us per step at d = 32
 // with four-lane groups)
@@ -511,37 +547,66 @@ bool small_epoch_supported(const daisy_bpr_ctx *ctx, const daisy_epoch_plan *pla
            (size_t)plan->batch_size * small_dpad(ctx->d, plan->batch_size) * sizeof(float) <= kSmallLdsRows;      // at least the user rows
 }
 
+// what a launch needs of one (context, plan) pair: the plan as the kernel reads it, the pitch of the staged rows, the
+// staging mode the LDS rule picks and the dynamic LDS it takes
+struct SmallShape {
+    SmallPlan pl;
+    int d, dpad, mode;
+    size_t shmem;
+};
+static SmallShape small_shape(const daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan) {
+    SmallShape sh;
+    sh.pl.ukey = plan->ukey;
+    sh.pl.ij = reinterpret_cast<const int2 *>(plan->uval);
+    sh.pl.ekey = plan->ekey;
+    sh.pl.esu = reinterpret_cast<const uint2 *>(plan->eval);
+    sh.pl.umask = plan->umask; sh.pl.imask = plan->imask;
+    sh.pl.n = plan->n; sh.pl.B = plan->batch_size; sh.pl.nb = plan->num_batches;
+    sh.d = ctx->d;
+    sh.dpad = small_dpad(sh.d, plan->batch_size);
+    const size_t row_bytes = (size_t)plan->batch_size * sh.dpad * sizeof(float);
+    sh.mode = (3 * row_bytes <= kSmallLdsRows) ? 3 : ((2 * row_bytes <= kSmallLdsRows) ? 2 : 1);
+    sh.shmem = (size_t)sh.mode * row_bytes;
+    return sh;
+}
+
+// Lane groups half as wide as dispatch_d's (a lane then holds two float4 of a row instead of one): twice as
+// many groups share the serial part of phase B - the run heads each group works through one after the other,
+// a chain of dependent LDS reads - which is what bounds a step here, not bytes.  Measured at B=256: d=32 8.9 ->
+// see profiles/r02_small_epoch.txt.
+static bool small_narrow() {
+    static const int tune_narrow = getenv("DAISY_SMALL_NARROW") ? atoi(getenv("DAISY_SMALL_NARROW")) : 1;
+    return tune_narrow != 0;
+}
+template <class F>
+static int dispatch_small(int d, F &&f) {
+    if (small_narrow() && d % 4 == 0 && d <= 128) {
+        if (d == 32) return f(RowCfg<4, 4, 2, true>{});
+        if (d == 64) return f(RowCfg<8, 4, 2, true>{});
+        if (d == 128) return f(RowCfg<8, 4, 4, true>{});
+        if (d <= 32) return f(RowCfg<4, 4, 2>{});
+        if (d <= 64) return f(RowCfg<8, 4, 2>{});
+        return f(RowCfg<8, 4, 4>{});
+    }
+    return dispatch_d(d, f);
+}
+
+// after an epoch that wrote the tables behind the context's back
+static void small_reset_cached(daisy_bpr_ctx *ctx) {
+    ctx->p_sqnorm_of = nullptr;          // P rows changed behind the staged step's row-norm cache
+    ctx->pre_ready = false;              // (and behind a pre-norm computed ahead of its step)
+    ctx->batch_set = false;
+    ctx->fwd_done = false;
+}
+
 int small_fit_epoch(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, float *P, float *Q, int loss_type, float gamma,
                     float lr, float reg_1, float reg_2, double *stats, double *epoch_acc, double *step_losses,
                     hipStream_t s, const SmallAdamArgs *adam) {
-    SmallPlan pl;
-    pl.ukey = plan->ukey;
-    pl.ij = reinterpret_cast<const int2 *>(plan->uval);
-    pl.ekey = plan->ekey;
-    pl.esu = reinterpret_cast<const uint2 *>(plan->eval);
-    pl.umask = plan->umask; pl.imask = plan->imask;
-    pl.n = plan->n; pl.B = plan->batch_size; pl.nb = plan->num_batches;
-    const int d = ctx->d, dpad = small_dpad(d, plan->batch_size);
-    const size_t row_bytes = (size_t)plan->batch_size * dpad * sizeof(float);
-    const int mode = (3 * row_bytes <= kSmallLdsRows) ? 3 : ((2 * row_bytes <= kSmallLdsRows) ? 2 : 1);
-    const size_t shmem = (size_t)mode * row_bytes;
-    // Lane groups half as wide as dispatch_d's (a lane then holds two float4 of a row instead of one): twice as
-    // many groups share the serial part of phase B - the run heads each group works through one after the other,
-    // a chain of dependent LDS reads - which is what bounds a step here, not bytes.  Measured at B=256: d=32 8.9 ->
-    // see profiles/r02_small_epoch.txt.
-    static const int tune_narrow = getenv("DAISY_SMALL_NARROW") ? atoi(getenv("DAISY_SMALL_NARROW")) : 1;
-    auto dispatch_small = [&](auto &&f) -> int {
-        if (tune_narrow && d % 4 == 0 && d <= 128) {
-            if (d == 32) return f(RowCfg<4, 4, 2, true>{});
-            if (d == 64) return f(RowCfg<8, 4, 2, true>{});
-            if (d == 128) return f(RowCfg<8, 4, 4, true>{});
-            if (d <= 32) return f(RowCfg<4, 4, 2>{});
-            if (d <= 64) return f(RowCfg<8, 4, 2>{});
-            return f(RowCfg<8, 4, 4>{});
-        }
-        return dispatch_d(d, f);
-    };
-    int rc = dispatch_small([&](auto cfg) -> int {
+    const SmallShape sh = small_shape(ctx, plan);
+    const SmallPlan &pl = sh.pl;
+    const int d = sh.d, dpad = sh.dpad, mode = sh.mode;
+    const size_t shmem = sh.shmem;
+    int rc = dispatch_small(d, [&](auto cfg) -> int {
         using C = decltype(cfg);
         SmallAdam ad{};
         int grid = 1;
@@ -580,10 +645,102 @@ int small_fit_epoch(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, float *P, 
     });
     if (rc) return rc;
     DAISY_LAUNCH_CHECK();
-    ctx->p_sqnorm_of = nullptr;          // P rows changed behind the staged step's row-norm cache
-    ctx->pre_ready = false;              // (and behind a pre-norm computed ahead of its step)
-    ctx->batch_set = false;
-    ctx->fwd_done = false;
+    small_reset_cached(ctx);
+    return DAISY_OK;
+}
+
+// One SGD epoch of `count` independent models: the trials are grouped by kernel instantiation (the RowCfg dispatch_small
+// picks for their d, the staging mode the LDS rule picks), every group is ONE launch of as many workgroups as it has
+// trials.  The argument records travel in the caller's device workspace: one copy per call, issued on the stream (out of
+// pageable host memory, so the runtime is done with the host vector when the copy call returns).  Everything is checked
+// before anything is launched.
+int small_fit_epoch_many(const daisy_small_trial *trials, int count, void *workspace, size_t workspace_bytes, hipStream_t s) {
+    struct Slot { int trial, key; size_t shmem; };
+    std::vector<Slot> order((size_t)count);
+    std::vector<SmallShape> shapes((size_t)count);
+    int device = -1;
+    for (int t = 0; t < count; ++t) {
+        const daisy_small_trial &tr = trials[t];
+        DAISY_CHECK_ARG(tr.ctx && tr.plan && tr.P && tr.Q && tr.stats && tr.epoch_acc, "fit_epoch_sgd_many: trial %d: NULL argument", t);
+        DAISY_CHECK_ARG(tr.plan->built, "fit_epoch_sgd_many: trial %d: plan has not been built", t);
+        DAISY_CHECK_ARG(small_epoch_supported(tr.ctx, tr.plan, tr.loss_type),
+                        "fit_epoch_sgd_many: trial %d: not a small-batch epoch (daisy_bpr_small_epoch_supported: sorted-layout "
+                        "plan, B <= %d, pairwise loss, no FM biases, rows that fit the LDS)", t, kSmallBatchMax);
+        DAISY_CHECK_ARG(tr.plan->U == tr.ctx->U && tr.plan->I == tr.ctx->I, "fit_epoch_sgd_many: trial %d: plan does not fit the context", t);
+    }
+    // what a trial writes belongs to it alone (a plan is only read: trials may share one)
+    {
+        std::vector<std::pair<const void *, int>> owned;
+        owned.reserve((size_t)count * 5);
+        for (int t = 0; t < count; ++t) {
+            const daisy_small_trial &tr = trials[t];
+            DAISY_CHECK_ARG(tr.P != tr.Q, "fit_epoch_sgd_many: trial %d: P and Q are the same table", t);
+            for (const void *p : {(const void *)tr.P, (const void *)tr.Q, (const void *)tr.stats, (const void *)tr.epoch_acc})
+                owned.emplace_back(p, t);
+        }
+        std::sort(owned.begin(), owned.end());
+        for (size_t x = 1; x < owned.size(); ++x)
+            DAISY_CHECK_ARG(owned[x].first != owned[x - 1].first,
+                            "fit_epoch_sgd_many: trial %d shares P, Q, stats or epoch_acc with trial %d",
+                            owned[x].second, owned[x - 1].second);
+    }
+    if (count == 0) return DAISY_OK;
+    for (int t = 0; t < count; ++t) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, trials[t].P) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("fit_epoch_sgd_many: trial %d: P is not a device pointer", t);
+            return DAISY_ERR_ARG;
+        }
+        if (t == 0) device = at.device;
+        DAISY_CHECK_ARG(at.device == device, "fit_epoch_sgd_many: trial %d is on device %d, trial 0 on device %d", t, at.device, device);
+    }
+    DAISY_CHECK_ARG(workspace && workspace_bytes >= (size_t)count * sizeof(SmallTrial),
+                    "fit_epoch_sgd_many: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0,
+                    (size_t)count * sizeof(SmallTrial));
+    for (int t = 0; t < count; ++t) {
+        shapes[t] = small_shape(trials[t].ctx, trials[t].plan);
+        int key = 0;
+        int rc = dispatch_small(shapes[t].d, [&](auto cfg) -> int {
+            using C = decltype(cfg);
+            key = ((C::LPR * 64 + C::VEC) * 64 + C::NV) * 2 + (C::EXACT ? 1 : 0);
+            return DAISY_OK;
+        });
+        if (rc) return rc;
+        order[t] = Slot{t, key * 4 + shapes[t].mode, shapes[t].shmem};
+    }
+    std::stable_sort(order.begin(), order.end(), [](const Slot &a, const Slot &b) { return a.key < b.key; });
+    std::vector<SmallTrial> recs((size_t)count);
+    for (int x = 0; x < count; ++x) {
+        const daisy_small_trial &tr = trials[order[x].trial];
+        const SmallShape &sh = shapes[order[x].trial];
+        recs[x] = SmallTrial{tr.P, tr.Q, sh.pl, sh.d, sh.dpad, tr.loss_type, tr.gamma, tr.lr, tr.reg_1, tr.reg_2,
+                             tr.stats, tr.epoch_acc, tr.step_losses};
+    }
+    SmallTrial *dev_recs = static_cast<SmallTrial *>(workspace);
+    DAISY_HIP(hipMemcpyAsync(dev_recs, recs.data(), recs.size() * sizeof(SmallTrial), hipMemcpyHostToDevice, s));
+    for (int lo = 0; lo < count;) {
+        int hi = lo;
+        size_t shmem = 0;
+        while (hi < count && order[hi].key == order[lo].key) { shmem = std::max(shmem, order[hi].shmem); ++hi; }
+        const int mode = shapes[order[lo].trial].mode, grid = hi - lo;
+        int rc = dispatch_small(shapes[order[lo].trial].d, [&](auto cfg) -> int {
+            using C = decltype(cfg);
+            auto launch = [&](auto kern) -> int {
+                DAISY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)kSmallLdsRows));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kSmallThreads), shmem, s, dev_recs + lo);
+                return DAISY_OK;
+            };
+            if (mode == 3) return launch(k_small_epoch_many<C, 3>);
+            if (mode == 2) return launch(k_small_epoch_many<C, 2>);
+            return launch(k_small_epoch_many<C, 1>);
+        });
+        if (rc) return rc;
+        DAISY_LAUNCH_CHECK();
+        lo = hi;
+    }
+    for (int t = 0; t < count; ++t) small_reset_cached(trials[t].ctx);
     return DAISY_OK;
 }
 

@@ -1129,4 +1129,12 @@ int daisy_bpr_fit_epoch_sgd(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, fl
     return DAISY_OK;
 }
 
+int daisy_bpr_fit_epoch_sgd_many(const daisy_small_trial *trials, int32_t count, void *workspace, size_t workspace_bytes,
+                                 daisy_stream_t stream) {
+    DAISY_CHECK_ARG(count >= 0, "fit_epoch_sgd_many: count=%d", count);
+    if (count == 0) return DAISY_OK;
+    DAISY_CHECK_ARG(trials != nullptr, "fit_epoch_sgd_many: trials is NULL");
+    return small_fit_epoch_many(trials, count, workspace, workspace_bytes, as_stream(stream));
+}
+
 }  // extern "C"

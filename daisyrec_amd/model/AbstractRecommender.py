@@ -356,22 +356,30 @@ class GeneralRecommender(AbstractRecommender):
         for epoch in (bar if bar is not None else epochs):
             self.train()
             current_loss, nonfinite = run_epoch(epoch)
-            if nonfinite > 0 or not math.isfinite(current_loss):
-                # AbstractRecommender.py:122-123 (checked once per epoch instead of per batch)
-                raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
-            self.epoch_losses.append(current_loss)
-            log_path = os.environ.get("DAISY_AMD_EPOCH_LOG")    # evidence trail of driver runs (tests/test_gpu_driver.py)
-            if log_path:
-                with open(log_path, "a") as fh:
-                    fh.write(f"{type(self).__name__} epoch {epoch} loss {current_loss!r}\n")
-            if bar is not None:
-                bar.set_description(f"[Epoch {epoch:03d}]")
-                bar.set_postfix(loss=current_loss)
-            self.eval()
-            if abs(current_loss - last_loss) < 1e-5 and self.early_stop:       # AbstractRecommender.py:132-137
-                self.logger.info("Satisfy early stop mechanism")
+            if self._close_epoch(epoch, current_loss, nonfinite, last_loss, bar):
                 break
             last_loss = current_loss
+
+    def _close_epoch(self, epoch, current_loss, nonfinite, last_loss, bar=None):
+        """What follows the training of epoch `epoch` (AbstractRecommender.py:122-123,130-137), for `_run_epochs` and for
+        model.fit_many, which trains the epochs of many models side by side: raises on a non-finite loss, records the
+        epoch's loss, leaves the model in eval mode; True when the early-stop rule ends the fit."""
+        if nonfinite > 0 or not math.isfinite(current_loss):
+            # AbstractRecommender.py:122-123 (checked once per epoch instead of per batch)
+            raise ValueError("Loss=Nan or Infinity: current settings does not fit the recommender")
+        self.epoch_losses.append(current_loss)
+        log_path = os.environ.get("DAISY_AMD_EPOCH_LOG")    # evidence trail of driver runs (tests/test_gpu_driver.py)
+        if log_path:
+            with open(log_path, "a") as fh:
+                fh.write(f"{type(self).__name__} epoch {epoch} loss {current_loss!r}\n")
+        if bar is not None:
+            bar.set_description(f"[Epoch {epoch:03d}]")
+            bar.set_postfix(loss=current_loss)
+        self.eval()
+        if abs(current_loss - last_loss) < 1e-5 and self.early_stop:       # AbstractRecommender.py:132-137
+            self.logger.info("Satisfy early stop mechanism")
+            return True
+        return False
 
     def _rank_loader(self, test_loader, topk_of):
         """The loop of every `rank`: topk_of(us [Bu], cands_ids [Bu, C]) -> int64 [Bu, topk] per batch of the loader;

@@ -14,3 +14,4 @@ from .IALSRecommender import IALS  # noqa: F401
 from .KNNCFRecommender import ItemKNNCF, UserKNNCF  # noqa: F401
 from .RP3betaRecommender import P3alpha, RP3beta  # noqa: F401
 from .PopRecommender import MostPop  # noqa: F401
+from ._many import fit_many  # noqa: F401

@@ -19,6 +19,7 @@ POINTWISE_LOSSES = (N.LOSS_CL, N.LOSS_SL)
 ITEM_MODES = {"atomic": N.ITEM_ATOMIC, "sorted": N.ITEM_SORTED, "chunked": N.ITEM_CHUNKED,
               "fused": N.ITEM_FUSED}
 SMALL_BATCH_MAX = 256      # kSmallBatchMax (csrc/bpr_internal.h): fit_epoch_sgd runs such epochs in one persistent workgroup
+SMALL_LDS_ROW_BYTES = 128 * 1024      # kSmallLdsRows (csrc/bpr_small.hip): a batch's user rows, float4-padded, must fit in it
 ORDER_MODES = {"identity": N.ORDER_IDENTITY, "perm": N.ORDER_PERM, "feistel": N.ORDER_FEISTEL}
 
 
@@ -423,6 +424,48 @@ class BprContext(_Native):
             _ptr(self.gQ, torch.float32, "gQ"), _ptr(self.stats, torch.float64, "stats"),
             _ptr(self.epoch_acc, torch.float64, "epoch_acc"),
             _ptr(step_losses, torch.float64, "step_losses"), int(item_mode), _stream()))
+
+
+def fit_epoch_sgd_many(trials, step_losses=None):
+    """One SGD epoch of many independent small-batch models in one native call (daisy_bpr_fit_epoch_sgd_many): one
+    workgroup per model, one launch per kernel shape.  `trials`: a list of (ctx, plan, P, Q, lr, reg_1, reg_2, loss_type,
+    gamma), each what `ctx.fit_epoch_sgd(plan, P, Q, ...)` takes; every context's `epoch_acc` and `stats` are written as
+    that call writes them, with the same bits.  step_losses: None, or one float64 tensor (or None) per trial with room
+    for its plan's batches.  Two trials may share a plan, but not P, Q or a context; ValueError names the trial."""
+    trials = list(trials)
+    count = len(trials)
+    if step_losses is None:
+        step_losses = [None] * count
+    if len(step_losses) != count:
+        raise ValueError(f"step_losses: {len(step_losses)} entries for {count} trials")
+    if count == 0:
+        check(lib.daisy_bpr_fit_epoch_sgd_many(None, 0, None, 0, _stream()))
+        return
+    recs = (N.SmallTrial * count)()
+    seen = {}
+    for t, (trial, sl) in enumerate(zip(trials, step_losses)):
+        ctx, plan, P, Q, lr, reg_1, reg_2, loss_type, gamma = trial
+        if id(ctx) in seen:
+            raise ValueError(f"fit_epoch_sgd_many: trial {t} shares its context (stats, epoch_acc) with trial {seen[id(ctx)]}")
+        seen[id(ctx)] = t
+        for W, rows, name in ((P, ctx.user_num, "P"), (Q, ctx.item_num, "Q")):
+            if not isinstance(W, torch.Tensor) or tuple(W.shape) != (rows, ctx.d):
+                raise ValueError(f"fit_epoch_sgd_many: trial {t}: {name} is not the [{rows}, {ctx.d}] table of its context")
+        if sl is not None and sl.numel() < plan.num_batches:
+            raise ValueError(f"fit_epoch_sgd_many: trial {t}: step_losses holds {sl.numel()} of {plan.num_batches} steps")
+        r = recs[t]
+        r.ctx, r.plan = ctx._h, plan._h
+        r.P, r.Q = _ptr(P, torch.float32, "P"), _ptr(Q, torch.float32, "Q")
+        r.loss_type, r.gamma, r.lr, r.reg_1, r.reg_2 = int(loss_type), float(gamma), float(lr), float(reg_1), float(reg_2)
+        r.stats, r.epoch_acc = _ptr(ctx.stats, torch.float64, "stats"), _ptr(ctx.epoch_acc, torch.float64, "epoch_acc")
+        r.step_losses = _ptr(sl, torch.float64, "step_losses")
+    ctx0 = trials[0][0]
+    with torch.cuda.device(ctx0.device):
+        ws = _ws(count * N.SMALL_TRIAL_WS_BYTES, ctx0.device)
+        check(lib.daisy_bpr_fit_epoch_sgd_many(recs, count, C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+    ctx0._many_ws = ws        # the kernels read it after this call returns: alive until the caller's next sync at least
+    for trial in trials:
+        trial[0]._p_key = None        # (the tables changed behind the row-norm cache, which the native side has dropped)
 
 
 def item_apply_counts(Q, g, cnt, lr, reg_1, reg_2, stats):

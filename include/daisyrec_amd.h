@@ -408,6 +408,27 @@ int daisy_bpr_fit_epoch_adam(daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, f
  * so that the rows a step references sat out a few steps, not thousands (its zero-gradient replay is the cost). */
 int daisy_bpr_small_epoch_supported(const daisy_bpr_ctx *ctx, const daisy_epoch_plan *plan, int32_t loss_type);
 
+/* One SGD epoch of MANY independent models in one call (a grid over lr / reg / factors, the folds of a cross-validation,
+ * the trials of a search: tune.py's `hyperopt_trail` x `fold_num` fits): the small-batch epoch keeps one workgroup - one CU -
+ * busy, so `count` models are `count` workgroups of one launch per kernel shape instead of `count` epochs one after another.
+ * Every trial is what one daisy_bpr_fit_epoch_sgd call takes (without gQ and the item mode) and ends with the same bits in
+ * P, Q, stats, epoch_acc and step_losses (may be NULL) as that call.  Every trial must be a small-batch epoch
+ * (daisy_bpr_small_epoch_supported & 1) whose plan fits its context; two trials may share a plan, which is only read, but
+ * not P, Q, stats or epoch_acc; all on one device.  A violation is DAISY_ERR_ARG naming the trial, before anything is
+ * launched.  workspace: device memory of at least count * DAISY_SMALL_TRIAL_WS_BYTES bytes, not reused before the
+ * stream has passed the call.  count == 0 is DAISY_OK. */
+#define DAISY_SMALL_TRIAL_WS_BYTES 192
+typedef struct daisy_small_trial {
+    daisy_bpr_ctx *ctx;
+    const daisy_epoch_plan *plan;
+    float *P, *Q;
+    int32_t loss_type;
+    float gamma, lr, reg_1, reg_2;
+    double *stats, *epoch_acc, *step_losses;
+} daisy_small_trial;
+int daisy_bpr_fit_epoch_sgd_many(const daisy_small_trial *trials, int32_t count, void *workspace, size_t workspace_bytes,
+                                 daisy_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Scoring / ranking  (MFRecommender.py:99-133)
  * ---------------------------------------------------------------------- */
